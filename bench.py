@@ -9,6 +9,12 @@ kernel, inputs resident on the GPU, results left in HBM. Ranks shard instances (
 
 Prints ONE JSON line (rank 0). See DESIGN.md §Measurement for the roofline model.
 
+A run without `--full` does what the headline needs: set up, warm up, time `--steps` steps, print the line.
+`--full` adds the legs beside it: the CPU baseline of the workload (the C oracle on this host's cores;
+`--no-cpu` leaves it out), on one GPU the pass of the statistics through libbftsim's RCCL all-reduce, and at
+N > 1 GPUs the weak-scaling run of cfg3 (`config.weak`). `--dump-outputs DIR` writes what the last timed step
+computed as DIR/<name>.npy (dump_outputs below): the inputs are seeded, so two builds compare array for array.
+
 `--workload cfg5` measures SURVEY §8d cfg5 instead (not the headline): N=7, 5 % drops, 10,000 heights,
 131,072 instances per GPU (1,048,576 on 8 GPUs), windowed rows (bftsim_set_window) with in-kernel
 hashes; the rounds-to-commit and commit-latency histograms are all-reduced over RCCL and printed.
@@ -255,6 +261,35 @@ def host_cpu() -> str:
     return f"{model} ({usable_cpus()} usable CPUs)"
 
 
+DUMP_BUDGET = 48 << 20                  # bytes of array data per --dump-outputs directory
+
+
+def dump_outputs(path: str, rank: int, arrays: dict) -> None:
+    """--dump-outputs: the arrays of the last timed step as <path>/<name>.npy (rank r > 0: <path>/rank<r>/). Every
+    array's first axis is the step's batch (instances / messages). float32 where the values are exact in it (8- and
+    16-bit integers), float64 otherwise (integers below 2^53). Where the whole batch would exceed DUMP_BUDGET, the
+    arrays of more than one dimension keep the same sorted sample of rows, drawn by a generator of fixed seed, and
+    sample_rows.npy holds their indices; the one-dimensional arrays are always whole."""
+    import numpy as np
+    d = path if rank == 0 else os.path.join(path, f"rank{rank}")
+    os.makedirs(d, exist_ok=True)
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    conv = {k: np.float32 if v.dtype.itemsize <= 2 else np.float64 for k, v in arrays.items()}
+    size = lambda k, rows: rows * int(np.prod(arrays[k].shape[1:], dtype=np.int64)) * np.dtype(conv[k]).itemsize
+    wide = [k for k, v in arrays.items() if v.ndim > 1]
+    left = DUMP_BUDGET - sum(size(k, len(v)) for k, v in arrays.items() if v.ndim == 1)
+    rows = None
+    if wide:
+        n = len(arrays[wide[0]])
+        assert all(len(arrays[k]) == n for k in wide), "arrays of one step share their batch axis"
+        keep = left // max(1, sum(size(k, 1) for k in wide))
+        if keep < n:
+            rows = np.sort(np.random.default_rng(0).choice(n, int(keep), replace=False))
+            np.save(os.path.join(d, "sample_rows.npy"), rows.astype(np.float64))
+    for k, v in arrays.items():
+        np.save(os.path.join(d, f"{k}.npy"), (v[rows] if rows is not None and v.ndim > 1 else v).astype(conv[k]))
+
+
 def _free_port() -> int:
     import socket
     with socket.socket() as so:
@@ -328,8 +363,16 @@ def main():
     ap.add_argument("--heights", type=int, default=None)
     ap.add_argument("--window", type=int, default=None, help="cfg5: canonical rows kept per instance (default "
                     "bftsim.configs.CFG5_WINDOW)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the CPU baseline of the workload (unless --no-cpu), the single-GPU pass "
+                         "through libbftsim's RCCL all-reduce, and at N > 1 GPUs the weak-scaling run of cfg3. A run "
+                         "without it sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / "
+                         "float64; a seeded sample of the rows where the whole would exceed 48 MB; rank r > 0 of a "
+                         "multi-GPU run writes DIR/rank<r>/)")
     ap.add_argument("--cpu-sample", type=int, default=None)
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--no-pipeline", action="store_true",
                     help="run each step's block-hash pass on the launch stream (no overlap across steps)")
     ap.add_argument("--pipeline-depth", type=int, default=None,
@@ -463,8 +506,12 @@ def main():
     # node-wide statistics: one RCCL all-reduce inside libbftsim (bftsim_stats_allreduce, over xGMI);
     # torch.distributed's all-reduce of the same counts only if librccl cannot be opened
     # (the decision is collective: every rank takes the same branch, capi_comm_init)
+    # (on one GPU the sum is the rank's own statistics; the pass through RCCL is part of --full)
     from bftsim.distributed import capi_comm_init
-    if capi_comm_init(sim, rank, world):
+    if world == 1 and not args.full:
+        tot = st
+        reduce_via = "none (one GPU; --full runs bftsim_stats_allreduce)"
+    elif capi_comm_init(sim, rank, world):
         tot = sim.stats_allreduce()
         reduce_via = "libbftsim bftsim_stats_allreduce (RCCL)"
     else:
@@ -482,10 +529,12 @@ def main():
     cms_sum, hms_sum, nl = sim.kernel_ms_sum()    # HIP events around every launch of the timed region
     cms = cms_sum / max(nl, 1)
     hms = hms_sum / max(nl, 1)
+    if args.dump_outputs:                 # the last timed launch, as a caller of launch + fetch receives it
+        dump_outputs(args.dump_outputs, rank, sim.fetch_summary() if c5 else sim.fetch())
 
-    # the weak counterpart of a multi-GPU strong headline: --instances per GPU on every rank, same K / W
+    # the weak counterpart of a multi-GPU strong headline (--full): --instances per GPU on every rank, same K / W
     weak = None
-    if args.scaling == "strong" and world > 1:
+    if args.full and args.scaling == "strong" and world > 1:
         Iw, first_w = args.instances, rank * args.instances
         if auto_depth:
             sim.set_pipeline(pipelined, timed_pipeline(Iw)[0])
@@ -624,7 +673,7 @@ def main():
                              "hash 14976 lane-ops per header (SURVEY.md 8d)",
             },
         }
-        if not args.no_cpu and world == 1:    # the CPU leg: rank 0 at N = 1 only
+        if args.full and not args.no_cpu and world == 1:    # the CPU leg: rank 0 at N = 1 only
             try:
                 out["cpu_baseline"] = cpu_baseline(cfg, args.cpu_sample, usable_cpus(), args.workload)
             except Exception as e:  # the baseline is reported, never the target
@@ -706,6 +755,9 @@ def main_crypto(args):
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt = float(tmax.item())
     cms, hms, nl = sim.kernel_ms_sum()
+    if args.dump_outputs:                 # the last launch's rows and its sign / recover pass
+        dump_outputs(args.dump_outputs, rank, {**sim.fetch(), "crypto_checksum": rep["checksum"],
+                                               "crypto_messages": rep["inst_messages"]})
     sim.close()
     if rank == 0:
         msgs, seals = rep["messages"], rep["seals"]
@@ -723,7 +775,7 @@ def main_crypto(args):
                        "mismatches": rep["mismatches"], "parallelism": f"instance-sharded x{world}"},
             "roofline": None,
         }
-        if not args.no_cpu:
+        if args.full and not args.no_cpu:
             try:
                 # the reference recovers each message at each of its N receivers (core.rs:314-322) and each
                 # seal at each receiver (commit.rs:94-100); priced at the C oracle's measured recovery rate
@@ -790,7 +842,7 @@ def main_sig(args):
     t0 = time.perf_counter()
     for e0, e1 in evs:
         e0.record()
-        sg.recover(digs, sigs, want_pub=False)
+        _, addr, ok = sg.recover(digs, sigs, want_pub=False)
         e1.record()
     torch.cuda.synchronize(dev)
     if world > 1:
@@ -801,6 +853,8 @@ def main_sig(args):
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt = float(tmax.item())
     kms = sum(a.elapsed_time(b) for a, b in evs) / len(evs)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, {"address": addr.cpu().numpy(), "ok": ok.cpu().numpy()})
     if rank == 0:
         achieved = SIG_RECOVER_MADS * n / (kms / 1e3) / 1e12
         out = {
@@ -815,7 +869,7 @@ def main_sig(args):
                          "traffic": None, "kernel_ms": kms,
                          "ops_model": f"{SIG_RECOVER_MADS} 32x32->64 multiply-adds per recovery (host-counted)"},
         }
-        if not args.no_cpu:
+        if args.full and not args.no_cpu:
             try:
                 d, s_ = digs.cpu().numpy(), sigs.cpu().numpy()
                 out["cpu_baseline"] = sig_cpu_baseline(d, s_, args.cpu_sample or 65536, min(16, os.cpu_count() or 1))
@@ -869,8 +923,9 @@ def main_wire(args):
     assert bool((ok2 == 1).all()) and torch.equal(fields["digest"], b["digest"])
 
     def step():
-        o, f, _, _, _ = cd.encode(b, cap=cap)
-        cd.decode(o, f)
+        o, f, s, m, _ = cd.encode(b, cap=cap)
+        return f, s, m, cd.decode(o, f)
+    last = (offs, sd, mh, (fields, ok2))
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize(dev)
@@ -881,7 +936,7 @@ def main_wire(args):
     t0 = time.perf_counter()
     for e0, e1 in evs:
         e0.record()
-        step()
+        last = step()
         e1.record()
     torch.cuda.synchronize(dev)
     if world > 1:
@@ -892,6 +947,15 @@ def main_wire(args):
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt = float(tmax.item())
     kms = sum(a.elapsed_time(c) for a, c in evs) / len(evs)
+    if args.dump_outputs:                 # per message: frame length, both digests, the decoded fields
+        f, s, m, (dec, dok) = last
+        dec = dict(dec)                   # an absent signature / seal leaves its row as allocated: written as zeros
+        dec["signature"] = dec["signature"] * dec["has_sig"][:, None]
+        dec["commit_seal"] = dec["commit_seal"] * dec["has_seal"][:, None]
+        dump_outputs(args.dump_outputs, rank, {
+            "frame_bytes": (f[1:] - f[:-1]).cpu().numpy(), "sign_digest": s.cpu().numpy(),
+            "message_hash": m.cpu().numpy(), "decode_ok": dok.cpu().numpy(),
+            **{f"decoded_{k}": v.cpu().numpy() for k, v in dec.items()}})
     if rank == 0:
         algo = wire_algo_bytes(total, n, int((code == 3).sum()))
         achieved = algo / (kms / 1e3) / 1e9
@@ -908,7 +972,7 @@ def main_wire(args):
                          "frac": achieved / (HBM_PEAK / 1e9), "traffic": None, "kernel_ms": kms,
                          "algorithmic_bytes_per_step": algo},
         }
-        if not args.no_cpu:
+        if args.full and not args.no_cpu:
             try:
                 out_j["cpu_baseline"] = wire_cpu_baseline(batch, args.cpu_sample or 20000)
             except Exception as e:
@@ -995,7 +1059,7 @@ def main_msgpath(args):
     t0 = time.perf_counter()
     e0.record()
     for _ in range(args.steps):
-        step()
+        addr, ok = step()
     e1.record()
     torch.cuda.synchronize(dev)
     if world > 1:
@@ -1006,6 +1070,8 @@ def main_msgpath(args):
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt = float(tmax.item())
     gpu_ms = e0.elapsed_time(e1) / args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, {"address": addr.cpu().numpy(), "ok": ok.cpu().numpy()})
     if rank == 0:
         mads = 2 * 69_848 + SIG_RECOVER_MADS                # two signatures + one recovery per message
         achieved = mads * n / (gpu_ms / 1e3) / 1e12

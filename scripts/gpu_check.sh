@@ -12,7 +12,7 @@ if [ -z "$NOSUITE" ]; then
   tail -3 $O/gpu_suite.log; [ $rc -eq 0 ] || exit $rc
 fi
 if [ -z "$NOBENCH" ]; then
-  timeout -k 10 300 python bench.py > $O/default.json 2> $O/default.err || { tail -5 $O/default.err; exit 1; }
+  timeout -k 10 300 python bench.py --full > $O/default.json 2> $O/default.err || { tail -5 $O/default.err; exit 1; }
   python3 -c "import json; d=json.load(open('$O/default.json')); print('default', '%.4g' % d['value'], d['unit'], d['roofline']['kernel_ms'])"
 fi
 IFS=';' read -ra STEPS_ <<< "$EXTRA"

@@ -12,7 +12,7 @@ STEPS=20 WARMUP=5 NAME=closing/cfg3 bash scripts/gpu_profile.sh cfg3 || exit 1
 for I in 2048 4096 8192; do
   STEPS=20 WARMUP=5 NAME=closing/cfg3_$I bash scripts/gpu_profile.sh cfg3 --instances $I || exit 1
 done
-timeout -k 10 300 python bench.py --seed-order le --steps 20 --warmup 5 > $O/cfg3le.json 2> $O/cfg3le.err || exit 1
+timeout -k 10 300 python bench.py --seed-order le --steps 20 --warmup 5 --full > $O/cfg3le.json 2> $O/cfg3le.err || exit 1
 python3 -c "import json; d=json.load(open('$O/cfg3le.json')); print('le', '%.4g' % d['value'])"
-timeout -k 10 300 python bench.py > $O/default.json 2> $O/default.err || exit 1
+timeout -k 10 300 python bench.py --full > $O/default.json 2> $O/default.err || exit 1
 python3 -c "import json; d=json.load(open('$O/default.json')); print('default', '%.4g' % d['value'], d['steps'], d['warmup'])"

@@ -44,7 +44,7 @@ D)
   for w in "cfg3" "cfg3 --instances 2048" "cfg3 --seed-order le" "cfg5 --steps 1 --warmup 0" "cfg2" "drop64 --steps 5 --warmup 1" \
            "cfg4 --n 256 --steps 5 --warmup 1" "cfg4 --n 128 --steps 5 --warmup 1" "sig" "crypto" "wire"; do
     n=$(echo $w | tr ' ' '_' | tr -d '-')
-    timeout -k 10 400 python bench.py --workload $w > $O/lines/$n.json 2> $O/lines/$n.err || { tail -5 $O/lines/$n.err; exit 1; }
+    timeout -k 10 400 python bench.py --workload $w --full > $O/lines/$n.json 2> $O/lines/$n.err || { tail -5 $O/lines/$n.err; exit 1; }
     python3 -c "import json; d=json.load(open('$O/lines/$n.json')); print('$n', '%.4g' % d['value'], d['unit'], (d.get('roofline') or {}).get('frac'))"
   done
   ;;

@@ -13,7 +13,7 @@ R=gpurun_out/prof/${NAME:-$W}
 mkdir -p $R
 S=${STEPS:-10}; PS=${PSTEPS:-3}; WU=${WARMUP:-2}; PWU=${PWARMUP:-1}
 lscpu | grep -E "Model name|^CPU\(s\)" > $R/host_cpu.txt; nproc > $R/host_nproc.txt
-timeout -k 10 600 python bench.py --workload $W $X --steps $S --warmup $WU > $R/bench.json 2> $R/bench.err && \
+timeout -k 10 600 python bench.py --workload $W $X --steps $S --warmup $WU --full > $R/bench.json 2> $R/bench.err && \
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $R/stats -o run --output-format csv -- python3 bench.py --workload $W $X --steps $S --warmup $WU --no-cpu > $R/stats.json 2> $R/stats.err && \
 timeout -s KILL 180 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $R/fetch -o run --output-format csv -- python3 bench.py --workload $W $X --steps $PS --warmup $PWU --no-cpu > $R/fetch.json 2> $R/fetch.err && \
 timeout -s KILL 180 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $R/write -o run --output-format csv -- python3 bench.py --workload $W $X --steps $PS --warmup $PWU --no-cpu > $R/write.json 2> $R/write.err && \
