@@ -62,6 +62,12 @@ def lib():
                                            ctypes.c_void_p]
         L.bftsim_crypto_verify.argtypes = [ctypes.c_void_p, ctypes.POINTER(_abi.CCryptoReport), ctypes.c_uint64,
                                            ctypes.c_void_p, ctypes.c_void_p]
+        L.bftsim_set_trace_keep.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        L.bftsim_trace_sizes.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]
+        L.bftsim_export_trace.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p,
+                                          ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                          ctypes.c_void_p]
+        L.bftsim_trace_last_ms.argtypes = [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_float)] * 3
         L.bftsim_launched_count.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64),
                                             ctypes.POINTER(ctypes.c_uint64)]
         L.bftsim_comm_init.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_char_p]
@@ -305,6 +311,42 @@ class Simulator:
                 row.append(bytes(buf[o:o + k]))
             out.append(row)
         return out
+
+    def set_trace_keep(self, on: bool):
+        """crypto_verify keeps on the device what export_trace needs, until the next launch (bftsim_set_trace_keep)."""
+        _check(self.h, lib().bftsim_set_trace_keep(self.h, 1 if on else 0), "bftsim_set_trace_keep")
+
+    def trace_sizes(self):
+        """(frames [n] u32, stream bytes [n] u64) per instance of the last launch's trace (after crypto_verify)."""
+        n = self.n_launched
+        fr, by = np.zeros(n, np.uint32), np.zeros(n, np.uint64)
+        _check(self.h, lib().bftsim_trace_sizes(self.h, n, fr.ctypes.data, by.ctypes.data), "bftsim_trace_sizes")
+        return fr, by
+
+    def export_trace(self, begin: int = 0, count: int = None):
+        """The signed wire frames of instances [begin, begin + count) of the last launch (default: to its end), as
+        a bftsim.trace.Trace (include/bftsim.h bftsim_export_trace, SPEC.md §11b)."""
+        from .trace import Trace
+        if count is None:
+            count = self.n_launched - begin
+        fr, by = self.trace_sizes()
+        if begin < 0 or count < 0 or begin + count > len(fr):
+            raise BftsimError(f"export_trace: instances [{begin}, {begin + count}) outside the last launch of {len(fr)}")
+        frames, nbytes = int(fr[begin:begin + count].sum()), int(by[begin:begin + count].sum())
+        stream = np.zeros(nbytes, np.uint8)
+        off = np.zeros(frames + 1, np.uint64)
+        meta = np.zeros((frames, 4), np.uint32)
+        f0 = np.zeros(count + 1, np.uint64)
+        _check(self.h, lib().bftsim_export_trace(self.h, begin, count, stream.ctypes.data, nbytes, off.ctypes.data,
+                                                 frames, meta.ctypes.data, f0.ctypes.data), "bftsim_export_trace")
+        return Trace(stream, off, meta, f0, begin)
+
+    def trace_ms(self):
+        """(size pass + scan, emit kernel, device-to-host copies) of the last trace calls, device ms."""
+        a, b, c = ctypes.c_float(), ctypes.c_float(), ctypes.c_float()
+        _check(self.h, lib().bftsim_trace_last_ms(self.h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)),
+               "bftsim_trace_last_ms")
+        return a.value, b.value, c.value
 
     @staticmethod
     def comm_available():

@@ -1,0 +1,102 @@
+"""The trace of a run (SPEC.md §11b): every consensus broadcast of the last launch as the signed wire frame a
+reference node would have read from its socket (include/bftsim.h bftsim_export_trace), and the receiver's side
+of it, composed from libbftwire and libbftsig."""
+from __future__ import annotations
+
+import numpy as np
+
+MT_PREPREPARE, MT_PREPARE, MT_COMMIT, MT_ROUND_CHANGE = 1, 2, 3, 4
+FLAG_FORGED, FLAG_WILD, FLAG_EQUIV, FLAG_OLD = 1, 2, 4, 8
+
+
+class Trace:
+    """Frames of instances [begin, begin + count) of a launch, in broadcast-log order.
+    stream [bytes] u8; frame_off [frames + 1] u64; meta [frames, 4] u32 (log word 0, log word 1, flags, instance
+    relative to begin); inst_frame0 [count + 1] u64."""
+
+    def __init__(self, stream, frame_off, meta, inst_frame0, begin=0):
+        self.stream, self.frame_off, self.meta, self.inst_frame0, self.begin = stream, frame_off, meta, inst_frame0, begin
+
+    def __len__(self):
+        return len(self.frame_off) - 1
+
+    tick = property(lambda self: self.meta[:, 0])
+    phase = property(lambda self: self.meta[:, 1] & 0xff)
+    code = property(lambda self: (self.meta[:, 1] >> 8) & 0xff)
+    sender = property(lambda self: self.meta[:, 1] >> 16)
+    flags = property(lambda self: self.meta[:, 2])
+    instance = property(lambda self: self.meta[:, 3])
+
+    def frame(self, k: int) -> bytes:
+        return bytes(self.stream[int(self.frame_off[k]):int(self.frame_off[k + 1])])
+
+    def frames(self, i: int) -> list:
+        """the frames of instance begin + i"""
+        return [self.frame(k) for k in range(int(self.inst_frame0[i]), int(self.inst_frame0[i + 1]))]
+
+    def instance_stream(self, i: int) -> np.ndarray:
+        """the bytes instance begin + i put on the wire (what bftwire_split_frames takes)"""
+        a, b = int(self.inst_frame0[i]), int(self.inst_frame0[i + 1])
+        return self.stream[int(self.frame_off[a]):int(self.frame_off[b])]
+
+
+def _gather(trace: Trace, idx: np.ndarray):
+    """the frames `idx` as a contiguous stream of their own -> (bytes, offsets)"""
+    off = trace.frame_off.astype(np.int64)
+    lens = off[idx + 1] - off[idx]
+    new = np.zeros(len(idx) + 1, np.int64)
+    np.cumsum(lens, out=new[1:])
+    src = np.repeat(off[idx] - new[:-1], lens) + np.arange(int(new[-1]), dtype=np.int64)
+    return trace.stream[src], new
+
+
+def audit(trace: Trace, addresses, codec, signer, decoded: dict = None) -> np.ndarray:
+    """What a receiver does with each frame (handle_message, core.rs:314-322): decode it, rebuild the sign payload
+    from the decoded fields (signature None), recover the signer and look it up in the validator set.
+    -> [frames] int32: the recovered validator's index in `addresses`, or -1 (not decodable, not recoverable, or
+    not a validator). codec / signer: bftsim.wire.Codec / bftsim.sig.Signer of the same device. `decoded` (a dict)
+    receives what the frames carried: signature [frames, 65], commit_seal [frames, 65], has_seal [frames]."""
+    t = codec.torch
+    out = np.full(len(trace), -1, np.int32)
+    addr = np.frombuffer(b"".join(bytes(a) for a in addresses), np.uint8).reshape(-1, 20)
+    rec = np.zeros((len(trace), 20), np.uint8)
+    good = np.zeros(len(trace), bool)
+    sig, seal, has_seal = np.zeros((len(trace), 65), np.uint8), np.zeros((len(trace), 65), np.uint8), np.zeros(len(trace), bool)
+    code = trace.code
+    # Subject frames: the Commits carry a seal, the others none (GossipMessage::commit_seal)
+    for sel, sealed in ((code == MT_COMMIT, True), ((code == MT_PREPARE) | (code == MT_ROUND_CHANGE), False)):
+        idx = np.nonzero(sel)[0]
+        if len(idx) == 0:
+            continue
+        sb, offs = _gather(trace, idx)
+        dec, ok = codec.decode(sb, offs)
+        rx = {k: dec[k] for k in ("code", "round", "height", "digest", "create_time")}
+        if sealed:
+            rx["commit_seal"] = dec["commit_seal"]
+        _, _, sd, _, ok2 = codec.encode(rx)
+        _, a, ok3 = signer.recover(sd, dec["signature"], want_pub=False)
+        want_seal = 1 if sealed else 0
+        fine = (ok == 1) & (ok2 == 1) & (ok3 == 1) & (dec["has_sig"] == 1) & (dec["has_seal"] == want_seal)
+        t.cuda.synchronize(codec.device)
+        rec[idx], good[idx] = a.cpu().numpy(), fine.cpu().numpy()
+        sig[idx], has_seal[idx] = dec["signature"].cpu().numpy(), dec["has_seal"].cpu().numpy() == 1
+        if sealed:
+            seal[idx] = dec["commit_seal"].cpu().numpy()
+    idx = np.nonzero(code == MT_PREPREPARE)[0]
+    if len(idx):
+        from . import wire
+        sb, offs = _gather(trace, idx)
+        arr, ok = codec.decode_preprepare(sb, offs)
+        ms = wire.array_to_preprepares(arr)
+        sigs = np.stack([np.frombuffer(m["signature"] or bytes(65), np.uint8) for m in ms])
+        _, _, sd, _, ok2 = codec.encode_preprepare(ms)
+        _, a, ok3 = signer.recover(sd, sigs, want_pub=False)
+        t.cuda.synchronize(codec.device)
+        has = np.array([m["signature"] is not None for m in ms])
+        rec[idx], sig[idx] = a.cpu().numpy(), sigs
+        good[idx] = (ok == 1) & (ok2.cpu().numpy() == 1) & (ok3.cpu().numpy() == 1) & has
+    if decoded is not None:
+        decoded.update(signature=sig, commit_seal=seal, has_seal=has_seal)
+    for v in range(len(addr)):
+        out[good & (rec == addr[v]).all(axis=1)] = v
+    return out

@@ -18,6 +18,7 @@
 #include <dlfcn.h>
 #include <unistd.h>
 #include <rccl/rccl.h>                 // types only: librccl is opened at bftsim_comm_init (dlopen)
+#include <hipcub/hipcub.hpp>
 
 #include <mutex>
 #include <string>
@@ -27,6 +28,7 @@
 #include "bft_hip.h"
 #include "bft_fast64.h"
 #include "bft_crypto.h"
+#include "bft_trace.h"
 
 namespace bft {
 
@@ -334,6 +336,131 @@ __global__ __launch_bounds__(64) void bft_export_votes_kernel(Params p, const ui
     lens[t] = (uint32_t)k;
 }
 
+// ------------------------------------------------------------------------------ the trace (SPEC.md §11b)
+// The signed wire frame of every logged broadcast (bftsim_export_trace), from what bftsim_crypto_verify kept:
+// a size pass (lane per message, the frame emitter of bft_trace.h with a counting functor), a scan, an emit pass.
+struct TraceArgs {
+    const uint32_t* mlog;
+    uint32_t cap;
+    // dense, per message: kept by bftsim_crypto_verify (bftsim_set_trace_keep)
+    const uint64_t* moff;             // [n_inst + 1]
+    const uint64_t* mref;
+    const uint8_t* raw;
+    const uint32_t* msg_k;
+    const uint8_t* sigs;
+    const uint8_t* seals;
+};
+// the frame inputs of dense message m; hbuf: this lane's LANE_HASH_BUF bytes (a Preprepare's header)
+__device__ inline trace::Msg trace_msg(const Params& p, const TraceArgs& a, uint64_t m, uint8_t* hbuf) {
+    const uint64_t ref = a.mref[m];
+    const uint32_t il = (uint32_t)(ref / a.cap);
+    const uint32_t* e = a.mlog + ref * MLOG_WORDS;
+    trace::Msg g;
+    g.code = (e[1] >> 8) & 0xffu;
+    g.ctime = trace::create_time(g.code, p.genesis_time, p.block_period, e[0]);
+    g.height = e[2];
+    g.round = e[3];
+    g.digest = a.raw + m * 32;
+    g.header = nullptr;
+    g.hlen = 0;
+    g.sig = a.sigs + m * 65;
+    g.seal = g.code == MT_COMMIT ? a.seals + (uint64_t)a.msg_k[m] * 65 : nullptr;
+    if (g.code == MT_PREPREPARE) {
+        const uint64_t b = (uint64_t)e[4] | ((uint64_t)e[5] << 32);
+        const uint32_t x = blk_h(b), prop = blk_prop(b), var = blk_var(b);
+        uint32_t prev[8];
+        crypto_parent(p, il, x, prev);
+        const uint64_t time = p.genesis_time + (uint64_t)p.block_period * ((uint64_t)blk_T(b) + 1ull);
+        g.hlen = header_raw((uint64_t*)hbuf, prev, p.addresses + 20u * prop, p.seed, p.first_instance + il, x, prop, var,
+                            time);
+        g.header = hbuf;
+    }
+    return g;
+}
+// size pass: lens[m] = the frame's length, lens[M] = 0 (the scan's last entry is the total)
+__global__ __launch_bounds__(64) void bft_trace_size_kernel(Params p, TraceArgs a, uint64_t M, uint64_t* lens) {
+    __shared__ __attribute__((aligned(16))) uint8_t hb[64 * LANE_HASH_BUF];
+    const uint64_t m = (uint64_t)blockIdx.x * 64u + threadIdx.x;
+    if (m >= M) { if (m == M) lens[M] = 0; return; }
+    lens[m] = trace::frame_len(trace_msg(p, a, m, hb + threadIdx.x * LANE_HASH_BUF));
+}
+// first byte of each instance: ioff[i] = foff[moff[i]], i <= n_inst
+__global__ __launch_bounds__(256) void bft_trace_inst_kernel(const uint64_t* moff, const uint64_t* foff, uint64_t n1,
+                                                             uint64_t* ioff) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (i < n1) ioff[i] = foff[moff[i]];
+}
+// {tick, phase | code << 8 | sender << 16, flags, instance - inst_begin} of messages [m0, m1)
+__global__ __launch_bounds__(256) void bft_trace_meta_kernel(TraceArgs a, uint64_t m0, uint64_t m1, uint32_t inst_begin,
+                                                             uint32_t* meta) {
+    const uint64_t m = m0 + (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (m >= m1) return;
+    const uint64_t ref = a.mref[m];
+    const uint32_t* e = a.mlog + ref * MLOG_WORDS;
+    ((uint4*)meta)[m - m0] = make_uint4(e[0], e[1], e[6], (uint32_t)(ref / a.cap) - inst_begin);
+}
+// emit pass, the serial shape (lane per frame, byte stores to global memory): the first correct version, kept
+// as the A/B baseline (BFTSIM_TESTING + BFTSIM_TRACE_SERIAL=1). `out` holds the frames of [m0, m1).
+__global__ __launch_bounds__(64) void bft_trace_emit_serial_kernel(Params p, TraceArgs a, uint64_t m0, uint64_t m1,
+                                                                   const uint64_t* foff, uint8_t* out, uint32_t* err) {
+    __shared__ __attribute__((aligned(16))) uint8_t hb[64 * LANE_HASH_BUF];
+    const uint64_t m = m0 + (uint64_t)blockIdx.x * 64u + threadIdx.x;
+    if (m >= m1) return;
+    const uint32_t len = (uint32_t)(foff[m + 1] - foff[m]);
+    if (trace::write_frame(out + (foff[m] - foff[m0]), len, trace_msg(p, a, m, hb + threadIdx.x * LANE_HASH_BUF)) != len)
+        atomicAdd(err, 1u);
+}
+// emit pass: a wave per 64 consecutive frames, which are one contiguous piece of the stream. Each lane expands
+// its frame into an LDS stage laid out like that piece (as many whole frames per round as the stage holds), then
+// the wave copies the stage out with coalesced 16-byte stores (byte stores for the unaligned head and tail).
+// Every lane's writes are bounded by its frame's counted length and the copy by the counted lengths of the
+// round's frames, so a disagreement of the two passes only counts in *err. Only a Preprepare needs a header
+// buffer: a round takes at most TRACE_PP of them, which keeps the block at 4 per CU.
+constexpr uint32_t TRACE_STAGE = 32 * 1024, TRACE_PP = 16;
+__global__ __launch_bounds__(64) void bft_trace_emit_kernel(Params p, TraceArgs a, uint64_t m0, uint64_t m1,
+                                                            const uint64_t* foff, uint8_t* out, uint32_t* err) {
+    __shared__ __attribute__((aligned(16))) uint8_t hb[TRACE_PP * LANE_HASH_BUF];
+    __shared__ __attribute__((aligned(16))) uint8_t stage[TRACE_STAGE];
+    const uint32_t lane = threadIdx.x;
+    const uint64_t mb = m0 + (uint64_t)blockIdx.x * 64u;
+    const uint32_t live = (uint32_t)(m1 - mb < 64u ? m1 - mb : 64u);
+    const uint64_t m = mb + (lane < live ? lane : live);        // idle lanes: the empty frame at the block's end
+    const uint64_t base = foff[m0];
+    const uint64_t o0 = foff[m] - base, o1 = foff[lane < live ? m + 1 : m] - base;
+    const bool pp = lane < live && ((a.mlog[a.mref[m] * MLOG_WORDS + 1] >> 8) & 0xffu) == (uint32_t)MT_PREPREPARE;
+    const uint64_t ppmask = __ballot(pp);
+    uint32_t first = 0;
+    while (first < live) {                                      // wave-uniform
+        const uint64_t r0 = __shfl(o0, (int)first);
+        const uint32_t shift = (uint32_t)(r0 & 15u);            // stage byte k = stream byte r0 - shift + k
+        // Preprepares among lanes [first, lane): this lane's header slot; both conditions ascend with the lane
+        const uint32_t slot = (uint32_t)__popcll((ppmask >> first) & ((1ull << (lane >= first ? lane - first : 0u)) - 1ull));
+        const bool fits = lane >= first && o1 - r0 + shift <= TRACE_STAGE && slot + (pp ? 1u : 0u) <= TRACE_PP;
+        const uint32_t cnt = (uint32_t)__popcll(__ballot(fits));    // a run of lanes from `first`
+        if (cnt == 0) {                                         // one frame above the stage: not produced by any log
+            if (lane == first) atomicAdd(err, 1u);
+            first += 1;
+            continue;
+        }
+        if (fits && lane < live) {
+            const uint32_t len = (uint32_t)(o1 - o0);
+            if (trace::write_frame(stage + shift + (uint32_t)(o0 - r0), len,
+                                   trace_msg(p, a, m, hb + (pp ? slot : 0u) * LANE_HASH_BUF)) != len)
+                atomicAdd(err, 1u);
+        }
+        __syncthreads();
+        const uint32_t end = shift + (uint32_t)(__shfl(o1, (int)(first + cnt - 1u)) - r0);
+        uint8_t* dst = out + (r0 - shift);                      // 16-byte aligned
+        const uint32_t hi = (shift + 15u) & ~15u;
+        const uint32_t b0 = hi < end ? hi : end, b1 = (end & ~15u) > b0 ? (end & ~15u) : b0;
+        if (shift + lane < b0) dst[shift + lane] = stage[shift + lane];
+        for (uint32_t k = b0 + 16u * lane; k < b1; k += 1024u) *(uint4*)(dst + k) = *(const uint4*)(stage + k);
+        if (b1 + lane < end) dst[b1 + lane] = stage[b1 + lane];
+        __syncthreads();
+        first += cnt;
+    }
+}
+
 }  // namespace bft
 
 #include "bft_host.h"
@@ -403,6 +530,15 @@ struct bftsim {
     uint8_t* d_vhas = nullptr;        // [last_n][H][N]
     uint64_t vsig_n = 0;              // instances d_vsig holds (0: no verify since the last launch)
     void* sig = nullptr;              // libbftsig handle (bftsig_t*)
+    // the trace (bftsim_set_trace_keep, SPEC.md §11b): what bftsim_crypto_verify kept of the last launch
+    bool trace_keep = false;
+    bool testing = false;             // BFTSIM_TESTING=1 at the last prepare: the A/B switches below are read at all
+    uint8_t* d_tkeep = nullptr;       // one allocation: moff, mref, raw, msg_k, sigs, seals (trace_args points into it)
+    bft::TraceArgs trace_args{};
+    uint64_t trace_n = 0, trace_M = 0;    // instances (0: nothing kept) and messages it holds
+    uint64_t* d_tfoff = nullptr;      // [M + 1] frame offsets, then [n + 1] instance offsets, then the error counter
+    std::vector<uint64_t> trace_moff, trace_ioff;   // host, [n + 1]: first message / first stream byte of each instance
+    float trace_ms[3] = {0, 0, 0};    // size pass + scan, emit kernel, device-to-host copies of the last calls
     uint8_t* d_tips = nullptr;        // [cap_inst * 32]
     uint32_t* d_rcs = nullptr;        // RoundChangeSet tables, rcs_words(seg) per wave / workgroup
     uint32_t* d_backlog = nullptr;    // replay mode: backlog slots, backlog_words(seg) per wave / workgroup
@@ -555,8 +691,17 @@ static void use_set0_scratch(bftsim* h) {
     h->d_resume_q = r.resume_q;
 }
 
+static void trace_drop(bftsim* h) {
+    if (!h->d_tkeep && !h->d_tfoff && h->trace_n == 0) return;   // the launch path: nothing kept, no HIP call
+    (void)hipFree(h->d_tkeep); (void)hipFree(h->d_tfoff);
+    h->d_tkeep = nullptr; h->d_tfoff = nullptr;
+    h->trace_n = h->trace_M = 0;
+    h->trace_moff.clear(); h->trace_ioff.clear();
+}
+
 static int sync_all(bftsim* h);
 static void free_bufs(bftsim* h) {
+    trace_drop(h);
     // a pending chain batch must not outlive its rows: callers sync_all first; a caller that did not (destroy)
     // runs the batch and waits for it here
     if (h->n_pend) (void)sync_all(h);
@@ -831,6 +976,7 @@ static bft::Params make_params(bftsim* h, uint64_t first, uint64_t n);
 int bftsim_prepare(bftsim_t* h, uint64_t n) {
     if (!h || n == 0 || n > (1ull << 31)) return fail(h, BFTSIM_EINVAL, "bad instance count");
     HIPCHECK(h, hipSetDevice(h->device));
+    trace_drop(h);
     if (n <= h->cap_inst) { h->n_req = n; return BFTSIM_OK; }
     if (h->last_n) if (int rc = sync_all(h)) return rc;   // the last launch may still use them
     free_bufs(h);
@@ -869,6 +1015,7 @@ int bftsim_prepare(bftsim_t* h, uint64_t n) {
     {
         const char* tst = getenv("BFTSIM_TESTING");
         const bool testing = tst && strcmp(tst, "1") == 0;
+        h->testing = testing;
         const char* cw = getenv("BFTSIM_CHAIN_WAVE_MAX");
         if (testing && cw) h->chain_wave_max = strtoull(cw, nullptr, 10);
         const char* cl = getenv("BFTSIM_CHAIN_LANE_MIN");
@@ -1287,6 +1434,7 @@ int bftsim_launch(bftsim_t* h, uint64_t first, void* stream) {
     }
     h->last_n = n;
     h->vsig_n = 0;
+    trace_drop(h);
     h->last_first = first;
     h->last_stream = s;
     return BFTSIM_OK;
@@ -1724,24 +1872,39 @@ int bftsim_crypto_verify(bftsim_t* h, bftsim_crypto_report* out, uint64_t capaci
     // device arrays of the pass (one allocation)
     const uint64_t Mx = M ? M : 1;
     const uint64_t sz_msg = 8 + 32 + 4 + 4 + 32 + 65 + 20 + 1, sz_cm = 32 + 32 + 4 + 65 + 1 + 20 + 4;
-    uint8_t* pool = nullptr;
-    const uint64_t bytes = n * 8 + Mx * (sz_msg + sz_cm) + n * 32 + 64 + 256;
-    HIPCHECK(h, hipMalloc(&pool, bytes));
-    uint8_t* q = pool;
-    auto take = [&](uint64_t b) { uint8_t* r = q; q += (b + 15) & ~15ull; return r; };
+    // trace keep (bftsim_set_trace_keep): what the export reads lives in an allocation of its own that the handle
+    // takes over; off: the same allocations as ever
+    trace_drop(h);
+    const bool keep = h->trace_keep;
+    if (keep) off.push_back(M);
+    uint8_t *pool = nullptr, *kpool = nullptr;
+    if (keep) HIPCHECK(h, hipMalloc(&kpool, (n + 1) * 8 + Mx * (8 + 32 + 4 + 65 + 65) + 6 * 16));
+    // with keep on the six kept arrays (182 B per message) are not in the temporary pool
+    const uint64_t bytes = n * 8 + Mx * (sz_msg + sz_cm - (keep ? 8 + 32 + 4 + 65 + 65 : 0)) + n * 32 + 64 + 256;
+    if (hipError_t pe = hipMalloc(&pool, bytes); pe != hipSuccess) {
+        (void)hipFree(kpool);
+        return fail(h, BFTSIM_EHIP, std::string("hipMalloc(&pool, bytes): ") + hipGetErrorString(pe));
+    }
+    uint8_t *q = pool, *kq = kpool;
+    auto take = [&](uint64_t b, bool kept = false) {
+        uint8_t*& c = kept && keep ? kq : q;
+        uint8_t* r = c;
+        c += (b + 15) & ~15ull;
+        return r;
+    };
     bft::CryptoArgs a{};
     a.mlog = h->d_mlog; a.mlog_n = h->d_mlog_n; a.cap = h->mlog_cap; a.n_val = h->cfg.n;
     for (int k = 0; k < 4; ++k) a.forged[k] = h->forged[k];
-    uint64_t* d_off = (uint64_t*)take(n * 8); a.moff = d_off;
-    a.mref = (uint64_t*)take(Mx * 8); a.raw = take(Mx * 32); a.key = (uint32_t*)take(Mx * 4);
-    a.msg_k = (uint32_t*)take(Mx * 4); a.sign_dig = take(Mx * 32); a.sigs = take(Mx * 65);
+    uint64_t* d_off = (uint64_t*)take(off.size() * 8, true); a.moff = d_off;
+    a.mref = (uint64_t*)take(Mx * 8, true); a.raw = take(Mx * 32, true); a.key = (uint32_t*)take(Mx * 4);
+    a.msg_k = (uint32_t*)take(Mx * 4, true); a.sign_dig = take(Mx * 32); a.sigs = take(Mx * 65, true);
     a.rec_addr = take(Mx * 20); a.rec_ok = take(Mx);
     a.seal_dig = take(Mx * 32); a.seal_raw = take(Mx * 32); a.seal_key = (uint32_t*)take(Mx * 4);
-    a.seals = take(Mx * 65); a.seal_ok = take(Mx); uint8_t* seal_addr = take(Mx * 20);
+    a.seals = take(Mx * 65, true); a.seal_ok = take(Mx); uint8_t* seal_addr = take(Mx * 20);
     uint8_t* sig_ok = take(Mx);
     a.ncm = (uint32_t*)take(4); a.inst_ck = (uint32_t*)take(n * 32); a.counts = (unsigned long long*)take(64);
     int rc = BFTSIM_OK;
-    hipError_t e = hipMemcpyAsync(d_off, off.data(), n * 8, hipMemcpyHostToDevice, s);
+    hipError_t e = hipMemcpyAsync(d_off, off.data(), off.size() * 8, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipMemsetAsync(a.ncm, 0, 4, s);
     if (e == hipSuccess) e = hipMemsetAsync(a.inst_ck, 0, n * 32, s);
     if (e == hipSuccess) e = hipMemsetAsync(a.counts, 0, 64, s);
@@ -1790,8 +1953,16 @@ int bftsim_crypto_verify(bftsim_t* h, bftsim_crypto_report* out, uint64_t capaci
     if (e == hipSuccess && rc == 0 && inst_checksum) e = hipMemcpyAsync(inst_checksum, a.inst_ck, n * 32, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     (void)hipFree(pool);
+    if (rc || e != hipSuccess) (void)hipFree(kpool);
     if (rc) return rc;
     if (e != hipSuccess) return fail(h, BFTSIM_EHIP, std::string("bftsim_crypto_verify: ") + hipGetErrorString(e));
+    if (keep) {
+        h->d_tkeep = kpool;
+        h->trace_args = bft::TraceArgs{h->d_mlog, h->mlog_cap, a.moff, a.mref, a.raw, a.msg_k, a.sigs, a.seals};
+        h->trace_n = n;
+        h->trace_M = M;
+        h->trace_moff = off;
+    }
     out->messages = c[0];
     out->seals = c[1];
     out->forged = c[2];
@@ -1829,6 +2000,172 @@ int bftsim_export_ledger(bftsim_t* h, uint64_t capacity, uint8_t* hdr, uint64_t 
 }
 
 uint64_t bftsim_ledger_slot_bytes(uint32_t n) { return ((uint64_t)BFTSIM_HEADER_SLOT + 3 + (uint64_t)n * 133 + 7) & ~7ull; }
+
+// ---- the trace (SPEC.md §11b)
+int bftsim_set_trace_keep(bftsim_t* h, int on) {
+    if (!h) return BFTSIM_EINVAL;
+    h->trace_keep = on != 0;
+    if (!on) {
+        HIPCHECK(h, hipSetDevice(h->device));
+        trace_drop(h);
+    }
+    return BFTSIM_OK;
+}
+
+static int trace_ready(bftsim* h, const char* what) {
+    if (!h->crypto) return fail(h, BFTSIM_EINVAL, std::string(what) + ": bftsim_set_crypto not called");
+    if (!h->trace_keep) return fail(h, BFTSIM_EINVAL, std::string(what) + ": bftsim_set_trace_keep is off");
+    if (h->trace_n == 0 || h->trace_n != h->last_n)
+        return fail(h, BFTSIM_EINVAL, std::string(what) + ": no trace kept: bftsim_crypto_verify after the launch first");
+    return BFTSIM_OK;
+}
+
+// size pass + scan over every kept message, once per verify: d_tfoff and the host's per-instance offsets
+static int trace_size_pass(bftsim* h) {
+    if (h->d_tfoff) return BFTSIM_OK;
+    const uint64_t n = h->trace_n, M = h->trace_M;
+    if (M + 1 > 0x7fffffffull) return fail(h, BFTSIM_EINVAL, "trace: too many messages for one scan");
+    HIPCHECK(h, hipSetDevice(h->device));
+    hipStream_t s = h->last_stream;
+    uint64_t *d = nullptr, *lens = nullptr;
+    void* tmp = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    size_t tb = 0;
+    hipError_t e = hipMalloc(&d, (M + 1 + n + 1) * 8 + 16);
+    if (e == hipSuccess) e = hipMalloc(&lens, (M + 1) * 8);
+    if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(nullptr, tb, lens, d, (int)(M + 1));
+    if (e == hipSuccess) e = hipMalloc(&tmp, tb ? tb : 16);
+    if (e == hipSuccess) e = hipEventCreate(&e0);
+    if (e == hipSuccess) e = hipEventCreate(&e1);
+    std::vector<uint64_t> ioff(n + 1);
+    if (e == hipSuccess) {
+        bft::Params p = make_params(h, h->last_first, n);
+        e = hipEventRecord(e0, s);
+        hipLaunchKernelGGL(bft::bft_trace_size_kernel, dim3((uint32_t)((M + 1 + 63) / 64)), dim3(64), 0, s, p,
+                           h->trace_args, M, lens);
+        if (e == hipSuccess) e = hipGetLastError();
+        if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(tmp, tb, lens, d, (int)(M + 1), s);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(bft::bft_trace_inst_kernel, dim3((uint32_t)((n + 1 + 255) / 256)), dim3(256), 0, s,
+                               h->trace_args.moff, d, n + 1, d + M + 1);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipEventRecord(e1, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(ioff.data(), d + M + 1, (n + 1) * 8, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e == hipSuccess) e = hipEventElapsedTime(&h->trace_ms[0], e0, e1);
+    }
+    (void)hipFree(lens); (void)hipFree(tmp);
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    if (e != hipSuccess) {
+        (void)hipFree(d);
+        return fail(h, BFTSIM_EHIP, std::string("trace size pass: ") + hipGetErrorString(e));
+    }
+    h->d_tfoff = d;
+    h->trace_ioff = std::move(ioff);
+    return BFTSIM_OK;
+}
+
+int bftsim_trace_sizes(bftsim_t* h, uint64_t capacity, uint32_t* inst_frames, uint64_t* inst_bytes) {
+    if (!h) return BFTSIM_EINVAL;
+    if (int rc = trace_ready(h, "bftsim_trace_sizes")) return rc;
+    if (int rc = check_launched(h, capacity, "bftsim_trace_sizes")) return rc;
+    if (int rc = trace_size_pass(h)) return rc;
+    for (uint64_t i = 0; i < h->trace_n; ++i) {
+        if (inst_frames) inst_frames[i] = (uint32_t)(h->trace_moff[i + 1] - h->trace_moff[i]);
+        if (inst_bytes) inst_bytes[i] = h->trace_ioff[i + 1] - h->trace_ioff[i];
+    }
+    return BFTSIM_OK;
+}
+
+int bftsim_export_trace(bftsim_t* h, uint64_t inst_begin, uint64_t inst_count, uint8_t* stream, uint64_t stream_cap,
+                        uint64_t* frame_off, uint64_t frame_cap, uint32_t* frame_meta, uint64_t* inst_frame0) {
+    if (!h) return BFTSIM_EINVAL;
+    if (!frame_off) return fail(h, BFTSIM_EINVAL, "bftsim_export_trace: null frame_off");
+    if (int rc = trace_ready(h, "bftsim_export_trace")) return rc;
+    const uint64_t n = h->trace_n;
+    if (inst_begin > n || inst_count > n - inst_begin)
+        return fail(h, BFTSIM_EINVAL, "bftsim_export_trace: instances [" + std::to_string(inst_begin) + ", +" +
+                                          std::to_string(inst_count) + ") outside the last launch of " + std::to_string(n));
+    if (int rc = trace_size_pass(h)) return rc;
+    const uint64_t m0 = h->trace_moff[inst_begin], m1 = h->trace_moff[inst_begin + inst_count];
+    const uint64_t frames = m1 - m0, bytes = h->trace_ioff[inst_begin + inst_count] - h->trace_ioff[inst_begin];
+    if (frame_cap < frames)
+        return fail(h, BFTSIM_EINVAL, "bftsim_export_trace: frame_cap " + std::to_string(frame_cap) + " < " +
+                                          std::to_string(frames) + " frames");
+    if (stream_cap < bytes || (bytes && !stream))
+        return fail(h, BFTSIM_EINVAL, "bftsim_export_trace: stream_cap " + std::to_string(stream_cap) + " < " +
+                                          std::to_string(bytes) + " bytes");
+    // the serial emitter: the A/B arm of scripts/trace_bench.py only. A handle prepared without BFTSIM_TESTING=1
+    // (the product path) reads no environment here; a testing handle reads the switch per call, so that the arms
+    // interleave
+    const char* ser = h->testing ? getenv("BFTSIM_TRACE_SERIAL") : nullptr;
+    const bool serial = ser && atoi(ser) == 1;
+    HIPCHECK(h, hipSetDevice(h->device));
+    hipStream_t s = h->last_stream;
+    uint8_t* d_out = nullptr;
+    uint32_t* d_meta = nullptr;
+    uint32_t* d_err = (uint32_t*)(h->d_tfoff + h->trace_M + 1 + n + 1);
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    uint32_t err = 0;
+    hipError_t e = hipMalloc(&d_out, bytes + 16);
+    if (e == hipSuccess && frame_meta && frames) e = hipMalloc(&d_meta, frames * 16);
+    for (int k = 0; k < 4 && e == hipSuccess; ++k) e = hipEventCreate(&ev[k]);
+    if (e == hipSuccess) e = hipMemsetAsync(d_err, 0, 4, s);
+    if (e == hipSuccess) e = hipEventRecord(ev[0], s);
+    if (e == hipSuccess && frames) {
+        bft::Params p = make_params(h, h->last_first, n);
+        const dim3 g((uint32_t)((frames + 63) / 64));
+        if (serial)
+            hipLaunchKernelGGL(bft::bft_trace_emit_serial_kernel, g, dim3(64), 0, s, p, h->trace_args, m0, m1, h->d_tfoff,
+                               d_out, d_err);
+        else
+            hipLaunchKernelGGL(bft::bft_trace_emit_kernel, g, dim3(64), 0, s, p, h->trace_args, m0, m1, h->d_tfoff, d_out,
+                               d_err);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipEventRecord(ev[1], s);
+    if (e == hipSuccess && d_meta) {
+        hipLaunchKernelGGL(bft::bft_trace_meta_kernel, dim3((uint32_t)((frames + 255) / 256)), dim3(256), 0, s,
+                           h->trace_args, m0, m1, (uint32_t)inst_begin, d_meta);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    // the passes agreed on every frame: only now is anything written to the caller's buffers
+    if (e == hipSuccess && err == 0) {
+        e = hipEventRecord(ev[2], s);
+        if (e == hipSuccess && bytes) e = hipMemcpyAsync(stream, d_out, bytes, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(frame_off, h->d_tfoff + m0, (frames + 1) * 8, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess && d_meta) e = hipMemcpyAsync(frame_meta, d_meta, frames * 16, hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipEventRecord(ev[3], s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e == hipSuccess) e = hipEventElapsedTime(&h->trace_ms[1], ev[0], ev[1]);
+        if (e == hipSuccess) e = hipEventElapsedTime(&h->trace_ms[2], ev[2], ev[3]);
+    }
+    (void)hipFree(d_out); (void)hipFree(d_meta);
+    for (int k = 0; k < 4; ++k)
+        if (ev[k]) (void)hipEventDestroy(ev[k]);
+    if (e != hipSuccess) return fail(h, BFTSIM_EHIP, std::string("bftsim_export_trace: ") + hipGetErrorString(e));
+    if (err)
+        return fail(h, BFTSIM_EHIP, "bftsim_export_trace: " + std::to_string(err) +
+                                        " frames whose emitted length differs from the counted one");
+    const uint64_t base = frame_off[0];
+    for (uint64_t k = 0; k <= frames; ++k) frame_off[k] -= base;
+    if (inst_frame0)
+        for (uint64_t i = 0; i <= inst_count; ++i) inst_frame0[i] = h->trace_moff[inst_begin + i] - m0;
+    return BFTSIM_OK;
+}
+
+int bftsim_trace_last_ms(bftsim_t* h, float* size_ms, float* emit_ms, float* copy_ms) {
+    if (!h) return BFTSIM_EINVAL;
+    if (size_ms) *size_ms = h->trace_ms[0];
+    if (emit_ms) *emit_ms = h->trace_ms[1];
+    if (copy_ms) *copy_ms = h->trace_ms[2];
+    return BFTSIM_OK;
+}
 
 int bftsim_stats_get(bftsim_t* h, bftsim_stats* out) {
     if (!h || !out) return BFTSIM_EINVAL;

@@ -123,8 +123,8 @@ int bftsim_launch(bftsim_t *h, uint64_t first_instance, void *hip_stream);   /* 
 int bftsim_sync(bftsim_t *h);
 int bftsim_fetch(bftsim_t *h, bftsim_result *out);
 /* the instance range of the last launch [first, first + n): the count bftsim_fetch, _fetch_summary,
- * _export_headers, _export_ledger and _crypto_verify write per-instance rows for (n = 0: nothing launched).
- * Every one of those takes the capacity of the caller's buffers (in instances) and refuses a short one
+ * _export_headers, _export_ledger, _crypto_verify and _trace_sizes write per-instance rows for (n = 0: nothing
+ * launched). Every one of those takes the capacity of the caller's buffers (in instances) and refuses a short one
  * with BFTSIM_EINVAL before writing anything (the reference's Result-returning boundary,
  * src/consensus/backend.rs:45-68) */
 int bftsim_launched_count(bftsim_t *h, uint64_t *first_instance, uint64_t *n_instances);
@@ -158,9 +158,10 @@ int bftsim_kernel_ms_sum(bftsim_t *h, double *consensus_ms, double *hash_ms, uin
  * internal hash streams (a chain is sequential in height: a launch's chains take ~1.5 ms however many
  * there are, so batching multiplies their throughput). Results of a launch are complete once bftsim_sync
  * returns (it also enqueues a partial hash batch); bftsim_fetch/_stats_get/_fetch_summary read the last
- * launch (and sync as they need). The HIP runtime needs a hardware queue per stream in use (the caller's,
- * two launch and two to four hash streams): GPU_MAX_HW_QUEUES >= 5 in the environment before HIP initialises (HIP's
- * default is 4; bench.py sets 8). Takes effect at the next bftsim_prepare (buffers are re-allocated). */
+ * launch (and sync as they need). The HIP runtime needs a hardware queue per stream in use: with the defaults that
+ * is six (the caller's, two launch and three hash streams; four launch streams with little-endian seeds), so
+ * GPU_MAX_HW_QUEUES >= 6 in the environment before HIP initialises (HIP's default is 4; bench.py sets 8). Takes
+ * effect at the next bftsim_prepare (buffers are re-allocated). */
 int bftsim_set_pipeline(bftsim_t *h, int on);
 /* pipelined launches: the number of consecutive launches whose block-hash chains run as one kernel (1..32,
  * default 4). A launch waiting for its batch is hashed when the batch fills, at bftsim_sync, or when the ring
@@ -237,6 +238,39 @@ int bftsim_crypto_verify(bftsim_t *h, bftsim_crypto_report *out, uint64_t capaci
  * block_hash per height this is the ledger's headers + block_hashes_by_height (store/schema.rs). */
 uint64_t bftsim_ledger_slot_bytes(uint32_t n_validators);
 int bftsim_export_ledger(bftsim_t *h, uint64_t capacity, uint8_t *hdr, uint64_t slot_bytes, uint32_t *hdr_len);
+
+/* the trace (real-crypto mode, SPEC.md §11b): the last launch's consensus traffic as the signed wire frames a
+ * reference node would have read from its socket. A frame is what TcpServer::broadcast writes for one logged
+ * broadcast: a 4-byte big-endian size, then RawMessage{Header{Consensus, ttl 10, create_time 0, peer_id None},
+ * payload}, the payload being the GossipMessage{code, create_time, msg, signature: Some, commit_seal} bytes; msg is
+ * Subject{view, digest} (Prepare, Commit, RoundChange) or PrePrepare{view, Block{header, transactions: []}}. Every
+ * value is the one bftsim_crypto_verify derived and the signature the one it computed (nothing is signed twice); a
+ * forged sender's frames are signed with keccak(secret). Every logged message has a frame, those dropped at the
+ * phase cap or sent by forged validators included; Blocks and Sync messages are not logged.
+ * bftsim_set_trace_keep (default 0): bftsim_crypto_verify keeps on the device what the export needs (each message's
+ * signature, each Commit's seal, the digests and the dense message index) until the next launch, prepare or
+ * destroy; its results are the same either way. */
+int bftsim_set_trace_keep(bftsim_t *h, int on);
+/* exact sizes of the last launch's trace (after bftsim_crypto_verify with keep on): frames and stream bytes per
+ * instance (either may be NULL); capacity = instances the buffers hold */
+int bftsim_trace_sizes(bftsim_t *h, uint64_t capacity, uint32_t *inst_frames, uint64_t *inst_bytes);
+/* the frames of instances [inst_begin, inst_begin + inst_count) of the last launch (indices into the launch), so
+ * that a large trace can be pulled in pieces; the device stream is allocated per call for that range. Host buffers:
+ *   stream      [stream_cap bytes] the frames back to back, instance by instance, in broadcast-log order
+ *   frame_off   [frame_cap + 1] byte offset of each frame in `stream`, then the total (what bftwire_split_frames
+ *               returns for the stream)
+ *   frame_meta  nullable, [frame_cap][4]: log word 0 (tick), log word 1 (phase | code << 8 | sender << 16),
+ *               log word 6 (flags: 1 forged, 2 wildcard digest, 4 equivocation, 8 old-block commit), instance
+ *               index relative to inst_begin
+ *   inst_frame0 nullable, [inst_count + 1] first frame index of each instance, then the frame count
+ * BFTSIM_EINVAL, with nothing written, when keep is off, no bftsim_crypto_verify ran since the launch, the range is
+ * outside the launch, or stream_cap / frame_cap is below the range's bytes / frames. BFTSIM_EHIP, with nothing
+ * written, if the emit pass disagrees with the size pass on any frame's length. */
+int bftsim_export_trace(bftsim_t *h, uint64_t inst_begin, uint64_t inst_count, uint8_t *stream, uint64_t stream_cap,
+                        uint64_t *frame_off, uint64_t frame_cap, uint32_t *frame_meta, uint64_t *inst_frame0);
+/* diagnostics, not part of the export's contract: device times (ms, HIP events) of the trace's last size pass + scan,
+ * emit kernel and device-to-host copies, as scripts/trace_bench.py records them */
+int bftsim_trace_last_ms(bftsim_t *h, float *size_ms, float *emit_ms, float *copy_ms);
 
 /* ValidatorSet / block helpers on the host (validator.rs, types/block.rs) */
 uint32_t bftsim_two_thirds_majority(uint32_t n);                    /* validator.rs:149-154 */
