@@ -40,6 +40,33 @@ class CCryptoReport(ctypes.Structure):
         "recoveries", "log_overflows")]
 
 
+class CAuditReport(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_uint64) for k in (
+        "frames", "ok", "undecodable", "unrecoverable", "not_validator", "seal_bad", "seal_foreign")] + [
+        ("by_code", ctypes.c_uint64 * 4)] + [(k, ctypes.c_uint64) for k in (
+            "out_of_range", "certified", "conflicts", "key_overflows", "recoveries")]
+
+
+class CAuditOut(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in (
+        "frame_status", "frame_signer", "inst_flags", "cert_round", "cert_digest", "cert_voters", "cert_frame",
+        "cert_flags")]
+
+
+def alloc_audit(frames: int, n_inst: int, heights: int):
+    """host buffers of bftsim_audit_out (certificate rows preset to "none") -> (struct, arrays)"""
+    rows = n_inst * heights
+    arrs = dict(
+        frame_status=np.zeros(frames, np.uint8), frame_signer=np.full(frames, -1, np.int32),
+        inst_flags=np.zeros(n_inst, np.uint32), cert_round=np.full(rows, 0xffff, np.uint16),
+        cert_digest=np.zeros(rows * 32, np.uint8), cert_voters=np.zeros(rows * 4, np.uint64),
+        cert_frame=np.zeros(rows, np.uint32), cert_flags=np.zeros(rows, np.uint8))
+    o = CAuditOut()
+    for k, a in arrs.items():
+        setattr(o, k, a.ctypes.data)
+    return o, arrs
+
+
 def to_cconfig(cfg: BftConfig):
     """Returns (struct, keepalive) — keep the second object alive while the struct is used."""
     c = CConfig()

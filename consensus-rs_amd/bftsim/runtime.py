@@ -68,6 +68,13 @@ def lib():
                                           ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
                                           ctypes.c_void_p]
         L.bftsim_trace_last_ms.argtypes = [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_float)] * 3
+        L.bftsim_audit_trace.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                         ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32,
+                                         ctypes.c_uint32, ctypes.POINTER(_abi.CAuditOut),
+                                         ctypes.POINTER(_abi.CAuditReport)]
+        L.bftsim_audit_last_trace.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32,
+                                              ctypes.POINTER(_abi.CAuditOut), ctypes.POINTER(_abi.CAuditReport)]
+        L.bftsim_audit_last_ms.argtypes = [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_float)] * 4
         L.bftsim_launched_count.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64),
                                             ctypes.POINTER(ctypes.c_uint64)]
         L.bftsim_comm_init.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_char_p]
@@ -347,6 +354,45 @@ class Simulator:
         _check(self.h, lib().bftsim_trace_last_ms(self.h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)),
                "bftsim_trace_last_ms")
         return a.value, b.value, c.value
+
+    def audit_trace(self, trace, max_heights: int = None, key_cap: int = 0):
+        """The observer (include/bftsim.h bftsim_audit_trace, SPEC.md §11c) over a bftsim.trace.Trace, or anything
+        with its stream / frame_off / inst_frame0: per-frame statuses and signers, per-height commit certificates and
+        the safety verdict, all computed on the device from the bytes. -> bftsim.trace.Audit"""
+        from .trace import Audit
+        H = self.cfg.heights if max_heights is None else max_heights
+        stream = np.ascontiguousarray(trace.stream, np.uint8)
+        off = np.ascontiguousarray(trace.frame_off, np.uint64)
+        f0 = np.ascontiguousarray(trace.inst_frame0, np.uint64)
+        frames, n = len(off) - 1, len(f0) - 1
+        ok = 0 < H <= 65535                        # the library refuses it; no buffers are sized by it here
+        o, arrs = _abi.alloc_audit(frames, n, H if ok else 0)
+        rep = _abi.CAuditReport()
+        _check(self.h, lib().bftsim_audit_trace(self.h, stream.ctypes.data, len(stream), off.ctypes.data, frames,
+                                                f0.ctypes.data, n, H, key_cap, ctypes.byref(o), ctypes.byref(rep)),
+               "bftsim_audit_trace")
+        return Audit(arrs, rep, n, H)
+
+    def audit_last_trace(self, begin: int = 0, count: int = None, key_cap: int = 0):
+        """The same over the kept trace of the last launch (after crypto_verify with set_trace_keep), instances
+        [begin, begin + count): emitted and audited on the device (bftsim_audit_last_trace)."""
+        from .trace import Audit
+        if count is None:
+            count = self.n_launched - begin
+        fr, _ = self.trace_sizes()
+        if begin < 0 or count < 0 or begin + count > len(fr):
+            raise BftsimError(f"audit_last_trace: instances [{begin}, {begin + count}) outside the last launch of {len(fr)}")
+        o, arrs = _abi.alloc_audit(int(fr[begin:begin + count].sum()), count, self.cfg.heights)
+        rep = _abi.CAuditReport()
+        _check(self.h, lib().bftsim_audit_last_trace(self.h, begin, count, key_cap, ctypes.byref(o), ctypes.byref(rep)),
+               "bftsim_audit_last_trace")
+        return Audit(arrs, rep, count, self.cfg.heights)
+
+    def audit_ms(self):
+        """(decode, recoveries, classify + tally, copies) of the last audit, device ms (bftsim_audit_last_ms)."""
+        v = [ctypes.c_float() for _ in range(4)]
+        _check(self.h, lib().bftsim_audit_last_ms(self.h, *[ctypes.byref(x) for x in v]), "bftsim_audit_last_ms")
+        return tuple(x.value for x in v)
 
     @staticmethod
     def comm_available():

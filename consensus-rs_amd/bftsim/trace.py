@@ -100,3 +100,61 @@ def audit(trace: Trace, addresses, codec, signer, decoded: dict = None) -> np.nd
     for v in range(len(addr)):
         out[good & (rec == addr[v]).all(axis=1)] = v
     return out
+
+
+# ---- the observer (SPEC.md §11c): bftsim_audit_trace / bftsim_audit_last_trace
+ST_OK, ST_UNDECODABLE, ST_UNRECOVERABLE, ST_NOT_VALIDATOR, ST_SEAL_BAD, ST_SEAL_FOREIGN = range(6)
+AUDIT_KEY_OVERFLOW, AUDIT_CONFLICT = 1, 2
+CERT_NONE = 0xffff
+
+
+class Audit:
+    """What the observer made of a frame stream: frame_status [frames] u8, frame_signer [frames] i32, inst_flags
+    [n] u32, and per (instance, height) the commit certificate: cert_round [n, H] u16 (CERT_NONE: none), cert_digest
+    [n, H, 32] u8, cert_voters [n, H, 4] u64, cert_frame [n, H] u32, cert_flags [n, H] u8 (1 proposed before
+    completion, 2 rightful proposer); report: bftsim_audit_report as a dict."""
+
+    def __init__(self, arrs: dict, rep, n: int, heights: int):
+        self.n, self.heights = n, heights
+        self.frame_status, self.frame_signer, self.inst_flags = arrs["frame_status"], arrs["frame_signer"], arrs["inst_flags"]
+        self.cert_round = arrs["cert_round"].reshape(n, heights)
+        self.cert_digest = arrs["cert_digest"].reshape(n, heights, 32)
+        self.cert_voters = arrs["cert_voters"].reshape(n, heights, 4)
+        self.cert_frame = arrs["cert_frame"].reshape(n, heights)
+        self.cert_flags = arrs["cert_flags"].reshape(n, heights)
+        self.report = {k: (list(getattr(rep, k)) if k == "by_code" else int(getattr(rep, k))) for k, _ in rep._fields_}
+
+    def voters(self, i: int, x: int) -> list:
+        """validator indices of the certificate of height x (1-based) of instance i"""
+        w = self.cert_voters[i, x - 1]
+        return [v for v in range(256) if (int(w[v >> 6]) >> (v & 63)) & 1]
+
+    def certificates(self, i: int) -> list:
+        """[(height, round, digest, voters, proposed, rightful)] of instance i, ascending height"""
+        out = []
+        for x in range(1, self.heights + 1):
+            r = int(self.cert_round[i, x - 1])
+            if r != CERT_NONE:
+                f = int(self.cert_flags[i, x - 1])
+                out.append((x, r, self.cert_digest[i, x - 1].tobytes(), self.voters(i, x), bool(f & 1), bool(f & 2)))
+        return out
+
+
+def compare(audit: Audit, result: dict, begin: int = 0) -> dict:
+    """The certificates against a run's result (Simulator.run / fetch; audit instance i = result instance begin + i).
+    Per instance, over the committed heights: `certified` with a certificate for the committed hash, `missing`
+    without one, `different` with one for another hash; `same_round` of the certified ones at the run's own round."""
+    n = audit.n
+    out = {k: np.zeros(n, np.uint32) for k in ("certified", "missing", "different", "same_round")}
+    for i in range(n):
+        ch = min(int(result["committed_height"][begin + i]), audit.heights)
+        for x in range(ch):
+            r = int(audit.cert_round[i, x])
+            if r == CERT_NONE:
+                out["missing"][i] += 1
+            elif np.array_equal(audit.cert_digest[i, x], result["block_hash"][begin + i, x]):
+                out["certified"][i] += 1
+                out["same_round"][i] += r == int(result["round"][begin + i, x])
+            else:
+                out["different"][i] += 1
+    return out

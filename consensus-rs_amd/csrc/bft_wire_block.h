@@ -237,7 +237,9 @@ BFT_FN bool rd_envelope(M& m, uint32_t want_code, uint64_t& ttl, uint64_t& rtime
     }
     return rd_arr(m, plen);
 }
-BFT_FN bool decode_pp_frame(const uint8_t* f, uint32_t len, bftwire_preprepare& d) {
+// *has_seal (nullable): whether the GossipMessage carried a commit_seal; seal_buf (nullable, 65 bytes): where it is read to
+BFT_FN bool decode_pp_frame(const uint8_t* f, uint32_t len, bftwire_preprepare& d, uint32_t* has_seal = nullptr,
+                            uint8_t* seal_buf = nullptr) {
     if (len < 4 || frame_size(f) != len - 4u) return false;
     Mem m{f + 4, len - 4u, 0};
     uint32_t plen, gn, idx, mlen;
@@ -252,10 +254,13 @@ BFT_FN bool decode_pp_frame(const uint8_t* f, uint32_t len, bftwire_preprepare& 
     if (!rd_uint(pm, d.round) || !rd_uint(pm, d.height) || !rd_block(pm, d.block)) return false;
     if (pm.left != 0 || pm.bad) return false;
     uint32_t present = 0;
-    uint8_t seal[65];
+    uint8_t seal_local[65];
+    uint8_t* seal = seal_buf ? seal_buf : seal_local;
     if (gn >= 4 && !rd_opt_bytes(g, 65, d.signature, present)) return false;
     d.has_sig = (uint8_t)present;
+    present = 0;
     if (gn >= 5 && !rd_opt_bytes(g, 65, seal, present)) return false;
+    if (has_seal) *has_seal = present;
     if (g.left != 0 || g.bad) return false;
     return m.i == m.n;
 }

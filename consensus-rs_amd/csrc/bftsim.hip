@@ -29,6 +29,7 @@
 #include "bft_fast64.h"
 #include "bft_crypto.h"
 #include "bft_trace.h"
+#include "bft_audit.h"
 
 namespace bft {
 
@@ -539,6 +540,7 @@ struct bftsim {
     uint64_t* d_tfoff = nullptr;      // [M + 1] frame offsets, then [n + 1] instance offsets, then the error counter
     std::vector<uint64_t> trace_moff, trace_ioff;   // host, [n + 1]: first message / first stream byte of each instance
     float trace_ms[3] = {0, 0, 0};    // size pass + scan, emit kernel, device-to-host copies of the last calls
+    float audit_ms[4] = {0, 0, 0, 0}; // decode, recoveries, classify + tally, copies of the last audit (SPEC.md §11c)
     uint8_t* d_tips = nullptr;        // [cap_inst * 32]
     uint32_t* d_rcs = nullptr;        // RoundChangeSet tables, rcs_words(seg) per wave / workgroup
     uint32_t* d_backlog = nullptr;    // replay mode: backlog slots, backlog_words(seg) per wave / workgroup
@@ -2164,6 +2166,216 @@ int bftsim_trace_last_ms(bftsim_t* h, float* size_ms, float* emit_ms, float* cop
     if (size_ms) *size_ms = h->trace_ms[0];
     if (emit_ms) *emit_ms = h->trace_ms[1];
     if (copy_ms) *copy_ms = h->trace_ms[2];
+    return BFTSIM_OK;
+}
+
+// ---- the observer (SPEC.md §11c): decode, recoveries, classification and tally of a frame stream on the device
+// libbftsig, opened as bftsim_set_crypto opens it; the observer needs no secrets
+static int audit_sig(bftsim* h) {
+    SigApi& a = sig_api();
+    if (!a.ok) return fail(h, BFTSIM_EUNSUPPORTED, a.why);
+    if (!h->sig && a.create(h->device, &h->sig) != 0) return fail(h, BFTSIM_EHIP, "bftsig_create failed");
+    return BFTSIM_OK;
+}
+// the passes over a device stream: frame k = d_stream[d_foff[k] - base, d_foff[k + 1] - base),
+// if0 on the host. Every temporary is freed before returning; only the caller's buffers and h->audit_ms are written.
+static int audit_device(bftsim* h, const uint8_t* d_stream, const uint64_t* d_foff, uint64_t base, uint64_t frames,
+                        const uint64_t* if0, uint64_t inst, uint32_t max_heights, uint32_t key_cap,
+                        const bftsim_audit_out* out, bftsim_audit_report* report, hipStream_t s, float copy_in_ms) {
+    namespace A = bft::audit;
+    SigApi& sa = sig_api();
+    if (key_cap == 0) key_cap = 4u * max_heights + 64u;
+    const uint64_t F = frames, Fx = F ? F : 1, Ix = inst ? inst : 1, rows = inst * max_heights, Rx = rows ? rows : 1;
+    if (key_cap > (1ull << 40) / sizeof(A::Key) / Ix)
+        return fail(h, BFTSIM_ENOMEM, "bftsim_audit: key_cap x instances above 1 TiB of key tables");
+    uint64_t bytes = 0;
+    auto sized = [&](uint64_t b) { const uint64_t o = bytes; bytes += (b + 31) & ~31ull; return o; };
+    const uint64_t o_st = sized(Fx), o_code = sized(Fx), o_hx = sized(Fx * 4), o_round = sized(Fx * 8), o_dig = sized(Fx * 32),
+                   o_sdig = sized(Fx * 32), o_sig = sized(Fx * 65), o_sk = sized(Fx * 4), o_want = sized(Fx * 4),
+                   o_sldig = sized(Fx * 32), o_seal = sized(Fx * 65), o_raddr = sized(Fx * 20), o_rok = sized(Fx),
+                   o_saddr = sized(Fx * 20), o_sok = sized(Fx), o_status = sized(Fx), o_signer = sized(Fx * 4),
+                   o_if0 = sized((inst + 1) * 8), o_keys = sized(Ix * key_cap * sizeof(A::Key)), o_iflags = sized(Ix * 4),
+                   o_cround = sized(Rx * 2), o_cdig = sized(Rx * 32), o_cvot = sized(Rx * 32), o_cframe = sized(Rx * 4),
+                   o_cflags = sized(Rx), o_counts = sized(A::CNT_WORDS * 8), o_nseal = sized(4);
+    uint8_t* pool = nullptr;
+    if (hipMalloc(&pool, bytes) != hipSuccess)
+        return fail(h, BFTSIM_ENOMEM, "bftsim_audit: " + std::to_string(bytes) + " bytes of device memory");
+    A::Recs r{pool + o_st, pool + o_code, (uint32_t*)(pool + o_hx), (uint64_t*)(pool + o_round), pool + o_dig, pool + o_sdig,
+              pool + o_sig, (uint32_t*)(pool + o_sk), (uint32_t*)(pool + o_want), pool + o_sldig, pool + o_seal};
+    unsigned long long* d_counts = (unsigned long long*)(pool + o_counts);
+    uint32_t* d_nseal = (uint32_t*)(pool + o_nseal);
+    uint64_t* d_if0 = (uint64_t*)(pool + o_if0);
+    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    hipError_t e = hipSuccess;
+    int rc = BFTSIM_OK;
+    for (int k = 0; k < 5 && e == hipSuccess; ++k) e = hipEventCreate(&ev[k]);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_if0, if0, (inst + 1) * 8, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemsetAsync(d_counts, 0, A::CNT_WORDS * 8 + 4, s);            // the counters and n_seals
+    if (e == hipSuccess) e = hipMemsetAsync(pool + o_cround, 0xff, Rx * 2, s);                // ROUND_NONE
+    if (e == hipSuccess) e = hipMemsetAsync(pool + o_cdig, 0, o_counts - o_cdig, s);          // the other certificate rows
+    if (e == hipSuccess) e = hipMemsetAsync(pool + o_iflags, 0, Ix * 4, s);
+    // decode
+    uint32_t n_seals = 0;
+    if (e == hipSuccess) e = hipEventRecord(ev[0], s);
+    if (e == hipSuccess)
+        e = A::launch_decode(A::DecodeArgs{d_stream, d_foff, base, F, h->d_addr, h->cfg.n,
+                                           h->cfg.seed_byte_order == BFTSIM_SEED_LE ? 1u : 0u, max_heights, r, d_nseal}, s);
+    if (e == hipSuccess) e = hipEventRecord(ev[1], s);
+    if (e == hipSuccess) e = hipMemcpyAsync(&n_seals, d_nseal, 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    // recoveries: every frame's signer, every decodable Commit's seal
+    if (e == hipSuccess && F && sa.recover(h->sig, r.sdig, r.sig, F, nullptr, pool + o_raddr, pool + o_rok, s) != 0)
+        rc = fail(h, BFTSIM_EHIP, std::string("bftsig_recover: ") + sa.last_error(h->sig));
+    if (e == hipSuccess && rc == 0 && n_seals &&
+        sa.recover(h->sig, r.seal_dig, r.seal, n_seals, nullptr, pool + o_saddr, pool + o_sok, s) != 0)
+        rc = fail(h, BFTSIM_EHIP, std::string("bftsig_recover (seals): ") + sa.last_error(h->sig));
+    if (e == hipSuccess && rc == 0) e = hipEventRecord(ev[2], s);
+    // classification and tally
+    uint8_t* d_status = pool + o_status;
+    int32_t* d_signer = (int32_t*)(pool + o_signer);
+    if (e == hipSuccess && rc == 0)
+        e = A::launch_classify(A::ClassifyArgs{r, F, h->d_addr, h->cfg.n, pool + o_raddr, pool + o_rok, pool + o_saddr,
+                                               pool + o_sok, d_status, d_signer, d_counts}, s);
+    if (e == hipSuccess && rc == 0)
+        e = A::launch_tally(A::TallyArgs{r, d_status, d_signer, d_if0, inst, (A::Key*)(pool + o_keys), key_cap, max_heights,
+                                         bftsim_two_thirds_majority(h->cfg.n), (uint32_t*)(pool + o_iflags),
+                                         (uint16_t*)(pool + o_cround), pool + o_cdig, (uint64_t*)(pool + o_cvot),
+                                         (uint32_t*)(pool + o_cframe), pool + o_cflags, d_counts}, s);
+    if (e == hipSuccess && rc == 0) e = hipEventRecord(ev[3], s);
+    unsigned long long c[A::CNT_WORDS] = {0};
+    if (e == hipSuccess && rc == 0) e = hipMemcpyAsync(c, d_counts, sizeof c, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && rc == 0) e = hipStreamSynchronize(s);      // every pass succeeded: only now the caller's buffers
+    if (e == hipSuccess && rc == 0 && out) {
+        auto back = [&](void* dst, uint64_t off, uint64_t b) {
+            if (dst && b && e == hipSuccess) e = hipMemcpyAsync(dst, pool + off, b, hipMemcpyDeviceToHost, s);
+        };
+        back(out->frame_status, o_status, F); back(out->frame_signer, o_signer, F * 4);
+        back(out->inst_flags, o_iflags, inst * 4);
+        back(out->cert_round, o_cround, rows * 2); back(out->cert_digest, o_cdig, rows * 32);
+        back(out->cert_voters, o_cvot, rows * 32); back(out->cert_frame, o_cframe, rows * 4);
+        back(out->cert_flags, o_cflags, rows);
+    }
+    if (e == hipSuccess && rc == 0) e = hipEventRecord(ev[4], s);
+    if (e == hipSuccess && rc == 0) e = hipStreamSynchronize(s);
+    float ms[4] = {0, 0, 0, 0};
+    for (int k = 0; k < 4 && e == hipSuccess && rc == 0; ++k) e = hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]);
+    (void)hipFree(pool);
+    for (int k = 0; k < 5; ++k)
+        if (ev[k]) (void)hipEventDestroy(ev[k]);
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(h, BFTSIM_EHIP, std::string("bftsim_audit: ") + hipGetErrorString(e));
+    h->audit_ms[0] = ms[0]; h->audit_ms[1] = ms[1]; h->audit_ms[2] = ms[2]; h->audit_ms[3] = ms[3] + copy_in_ms;
+    memset(report, 0, sizeof *report);
+    report->frames = F;
+    report->ok = c[A::CNT_STATUS + 0]; report->undecodable = c[A::CNT_STATUS + 1]; report->unrecoverable = c[A::CNT_STATUS + 2];
+    report->not_validator = c[A::CNT_STATUS + 3]; report->seal_bad = c[A::CNT_STATUS + 4];
+    report->seal_foreign = c[A::CNT_STATUS + 5];
+    for (int k = 0; k < 4; ++k) report->by_code[k] = c[A::CNT_CODE + k];
+    report->out_of_range = c[A::CNT_OUT_OF_RANGE];
+    report->certified = c[A::CNT_CERTIFIED];
+    report->conflicts = c[A::CNT_CONFLICTS];
+    report->key_overflows = c[A::CNT_KEY_OVERFLOWS];
+    report->recoveries = F + n_seals;
+    return BFTSIM_OK;
+}
+static int audit_dims(bftsim* h, uint64_t frames, uint64_t inst, uint32_t max_heights, const char* what) {
+    if (max_heights == 0 || max_heights > 65535u) return fail(h, BFTSIM_EINVAL, std::string(what) + ": max_heights outside 1..65535");
+    if (frames >= (1ull << 32)) return fail(h, BFTSIM_EINVAL, std::string(what) + ": 2^32 frames or more");
+    if (inst >= (1ull << 31)) return fail(h, BFTSIM_EINVAL, std::string(what) + ": 2^31 instances or more");
+    return BFTSIM_OK;
+}
+
+int bftsim_audit_trace(bftsim_t* h, const uint8_t* stream, uint64_t stream_bytes, const uint64_t* frame_off, uint64_t frames,
+                       const uint64_t* inst_frame0, uint64_t inst_count, uint32_t max_heights, uint32_t key_cap,
+                       const bftsim_audit_out* out, bftsim_audit_report* report) {
+    if (!h || !report) return BFTSIM_EINVAL;
+    if (!frame_off || !inst_frame0 || (stream_bytes && !stream))
+        return fail(h, BFTSIM_EINVAL, "bftsim_audit_trace: null stream, frame_off or inst_frame0");
+    if (int rc = audit_dims(h, frames, inst_count, max_heights, "bftsim_audit_trace")) return rc;
+    for (uint64_t k = 0; k < frames; ++k)
+        if (frame_off[k] > frame_off[k + 1]) return fail(h, BFTSIM_EINVAL, "bftsim_audit_trace: frame_off decreases");
+    if (frame_off[frames] != stream_bytes) return fail(h, BFTSIM_EINVAL, "bftsim_audit_trace: frame_off does not end at stream_bytes");
+    for (uint64_t i = 0; i < inst_count; ++i)
+        if (inst_frame0[i] > inst_frame0[i + 1]) return fail(h, BFTSIM_EINVAL, "bftsim_audit_trace: inst_frame0 decreases");
+    if (inst_frame0[0] != 0 || inst_frame0[inst_count] != frames)
+        return fail(h, BFTSIM_EINVAL, "bftsim_audit_trace: inst_frame0 does not run from 0 to frames");
+    HIPCHECK(h, hipSetDevice(h->device));
+    if (int rc = audit_sig(h)) return rc;
+    hipStream_t s = h->last_stream;
+    uint8_t* d_in = nullptr;
+    const uint64_t sb = (stream_bytes + 15) & ~15ull;              // the frame offsets follow the padded stream
+    if (hipMalloc(&d_in, sb + 16 + (frames + 1) * 8) != hipSuccess)
+        return fail(h, BFTSIM_ENOMEM, "bftsim_audit_trace: device memory for the stream");
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    float copy_ms = 0;
+    hipError_t e = hipEventCreate(&e0);
+    if (e == hipSuccess) e = hipEventCreate(&e1);
+    if (e == hipSuccess) e = hipEventRecord(e0, s);
+    if (e == hipSuccess && stream_bytes) e = hipMemcpyAsync(d_in, stream, stream_bytes, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_in + sb + 16, frame_off, (frames + 1) * 8, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipEventRecord(e1, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = hipEventElapsedTime(&copy_ms, e0, e1);
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    int rc = BFTSIM_OK;
+    if (e != hipSuccess) rc = fail(h, BFTSIM_EHIP, std::string("bftsim_audit_trace: ") + hipGetErrorString(e));
+    if (rc == 0)
+        rc = audit_device(h, d_in, (const uint64_t*)(d_in + sb + 16), 0, frames, inst_frame0, inst_count, max_heights, key_cap,
+                          out, report, s, copy_ms);
+    (void)hipFree(d_in);
+    return rc;
+}
+
+int bftsim_audit_last_trace(bftsim_t* h, uint64_t inst_begin, uint64_t inst_count, uint32_t key_cap,
+                            const bftsim_audit_out* out, bftsim_audit_report* report) {
+    if (!h || !report) return BFTSIM_EINVAL;
+    if (int rc = trace_ready(h, "bftsim_audit_last_trace")) return rc;
+    const uint64_t n = h->trace_n;
+    if (inst_begin > n || inst_count > n - inst_begin)
+        return fail(h, BFTSIM_EINVAL, "bftsim_audit_last_trace: instances [" + std::to_string(inst_begin) + ", +" +
+                                          std::to_string(inst_count) + ") outside the last launch of " + std::to_string(n));
+    if (int rc = trace_size_pass(h)) return rc;
+    const uint64_t m0 = h->trace_moff[inst_begin], m1 = h->trace_moff[inst_begin + inst_count];
+    const uint64_t frames = m1 - m0, base = h->trace_ioff[inst_begin], bytes = h->trace_ioff[inst_begin + inst_count] - base;
+    if (int rc = audit_dims(h, frames, inst_count, h->cfg.heights, "bftsim_audit_last_trace")) return rc;
+    HIPCHECK(h, hipSetDevice(h->device));
+    if (int rc = audit_sig(h)) return rc;
+    hipStream_t s = h->last_stream;
+    std::vector<uint64_t> if0(inst_count + 1);
+    for (uint64_t i = 0; i <= inst_count; ++i) if0[i] = h->trace_moff[inst_begin + i] - m0;
+    // the emit pass of bftsim_export_trace into a device stream that stays on the device
+    uint8_t* d_out = nullptr;
+    uint32_t* d_err = (uint32_t*)(h->d_tfoff + h->trace_M + 1 + n + 1);
+    uint32_t err = 0;
+    if (hipMalloc(&d_out, ((bytes + 15) & ~15ull) + 16) != hipSuccess)
+        return fail(h, BFTSIM_ENOMEM, "bftsim_audit_last_trace: device memory for the stream");
+    hipError_t e = hipMemsetAsync(d_err, 0, 4, s);
+    if (e == hipSuccess && frames) {
+        bft::Params p = make_params(h, h->last_first, n);
+        hipLaunchKernelGGL(bft::bft_trace_emit_kernel, dim3((uint32_t)((frames + 63) / 64)), dim3(64), 0, s, p, h->trace_args,
+                           m0, m1, h->d_tfoff, d_out, d_err);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    int rc = BFTSIM_OK;
+    if (e != hipSuccess) rc = fail(h, BFTSIM_EHIP, std::string("bftsim_audit_last_trace: ") + hipGetErrorString(e));
+    else if (err) rc = fail(h, BFTSIM_EHIP, "bftsim_audit_last_trace: " + std::to_string(err) +
+                                               " frames whose emitted length differs from the counted one");
+    if (rc == 0)
+        rc = audit_device(h, d_out, h->d_tfoff + m0, base, frames, if0.data(), inst_count, h->cfg.heights, key_cap, out,
+                          report, s, 0.f);
+    (void)hipFree(d_out);
+    return rc;
+}
+
+int bftsim_audit_last_ms(bftsim_t* h, float* decode_ms, float* recover_ms, float* tally_ms, float* copy_ms) {
+    if (!h) return BFTSIM_EINVAL;
+    if (decode_ms) *decode_ms = h->audit_ms[0];
+    if (recover_ms) *recover_ms = h->audit_ms[1];
+    if (tally_ms) *tally_ms = h->audit_ms[2];
+    if (copy_ms) *copy_ms = h->audit_ms[3];
     return BFTSIM_OK;
 }
 

@@ -272,6 +272,68 @@ int bftsim_export_trace(bftsim_t *h, uint64_t inst_begin, uint64_t inst_count, u
  * emit kernel and device-to-host copies, as scripts/trace_bench.py records them */
 int bftsim_trace_last_ms(bftsim_t *h, float *size_ms, float *emit_ms, float *copy_ms);
 
+/* the observer (SPEC.md §11c): a frame stream in the export's format, audited from its bytes on the device. Per frame:
+ * decode (every read bounded by the frame's span in frame_off; the bytes are untrusted), the sign payload rebuilt from
+ * the decoded fields with signature None, its signer recovered and looked up in the handle's validator set, and for a
+ * Commit the seal (keccak(0x03 || digest), types/votes.rs:94-101) recovered and compared with the signer. Per
+ * instance, in frame order, over the accepted frames (status OK or SEAL_FOREIGN): a tally of the Commit votes per
+ * (height, round, digest), a commit certificate per height (the first key whose voters exceed
+ * bftsim_two_thirds_majority(N)) and a safety verdict (a second digest with a quorum at a certified height).
+ * The validator set, N and seed_byte_order are the handle's config; no secrets are needed and bftsim_set_crypto need
+ * not have been called (libbftsig.so must be next to libbftsim.so). The handle's run state is untouched.
+ * frame status (one byte per frame, the first matching row wins): */
+#define BFTSIM_AUDIT_OK 0u             /* decodes; the signature recovers to validator `signer`; a Commit's seal too */
+#define BFTSIM_AUDIT_UNDECODABLE 1u    /* span under 4 bytes or size prefix != span - 4; not a Consensus RawMessage; the
+                                          GossipMessage or its msg does not parse or has trailing bytes; code outside
+                                          1..4; signature None; a Commit without a seal, another message with one */
+#define BFTSIM_AUDIT_UNRECOVERABLE 2u  /* the signature does not recover */
+#define BFTSIM_AUDIT_NOT_VALIDATOR 3u  /* it recovers to an address outside the set (every forged sender's frame) */
+#define BFTSIM_AUDIT_SEAL_BAD 4u       /* Commit whose seal does not recover (dropped by the reference, commit.rs:94-100) */
+#define BFTSIM_AUDIT_SEAL_FOREIGN 5u   /* Commit whose seal recovers to another address: accepted, counted apart */
+/* instance flags */
+#define BFTSIM_AUDIT_KEY_OVERFLOW 1u   /* a frame's key was absent from a full key table: the frame was ignored */
+#define BFTSIM_AUDIT_CONFLICT 2u       /* two digests with a quorum of Commits at one height (wire-level BFTSIM_FLAG_SAFETY) */
+struct bftsim_audit_report {
+    uint64_t frames, ok, undecodable, unrecoverable, not_validator, seal_bad, seal_foreign;
+    uint64_t by_code[4];        /* accepted frames per MessageType */
+    uint64_t out_of_range;      /* accepted PrePrepare/Commit frames with height 0 or > max_heights */
+    uint64_t certified;         /* (instance, height) pairs with a certificate */
+    uint64_t conflicts, key_overflows;
+    uint64_t recoveries;        /* ECDSA recoveries performed */
+};
+typedef struct bftsim_audit_report bftsim_audit_report;
+struct bftsim_audit_out {       /* host, caller-owned, any pointer may be NULL */
+    uint8_t *frame_status; int32_t *frame_signer;                 /* [frames]; signer: validator index for status 0, 4, 5, else -1 */
+    uint32_t *inst_flags;                                          /* [inst_count] BFTSIM_AUDIT_KEY_OVERFLOW | _CONFLICT */
+    uint16_t *cert_round; uint8_t *cert_digest; uint64_t *cert_voters;
+    uint32_t *cert_frame; uint8_t *cert_flags;                     /* [inst_count * max_heights] (x32, x4), row
+                                                                      inst * max_heights + height - 1: round (0xffff:
+                                                                      no certificate; rounds above 0xfffe read 0xfffe),
+                                                                      digest, voter bitmap, the completing frame's index
+                                                                      within the instance, flags (1 proposed before
+                                                                      completion, 2 by the rightful proposer) */
+};
+typedef struct bftsim_audit_out bftsim_audit_out;
+/* stream [stream_bytes]: frames back to back; frame_off [frames + 1]: byte offset of each frame, then the total;
+ * inst_frame0 [inst_count + 1]: first frame of each instance, then the frame count (what bftsim_export_trace writes).
+ * key_cap: keys per instance's table (0 = 4 * max_heights + 64); nothing is evicted. Arguments are checked before
+ * any device work and a refused call writes nothing: BFTSIM_EINVAL for a null handle, report, frame_off or
+ * inst_frame0, a frame_off that decreases or does not end at stream_bytes, an inst_frame0 that decreases or does not
+ * run from 0 to frames, max_heights of 0 or above 65,535, 2^32 frames or more, 2^31 instances or more. Hostile frame
+ * contents are never an error of the call: they become statuses. */
+int bftsim_audit_trace(bftsim_t *h, const uint8_t *stream, uint64_t stream_bytes, const uint64_t *frame_off, uint64_t frames,
+                       const uint64_t *inst_frame0, uint64_t inst_count, uint32_t max_heights, uint32_t key_cap,
+                       const bftsim_audit_out *out, bftsim_audit_report *report);
+/* the kept trace of the last launch (bftsim_set_trace_keep on, after bftsim_crypto_verify), instances
+ * [inst_begin, inst_begin + inst_count): emitted and audited on the device, no stream copy to the host;
+ * frame counts as bftsim_trace_sizes gives them; max_heights = config.heights. Refuses what bftsim_export_trace
+ * refuses. */
+int bftsim_audit_last_trace(bftsim_t *h, uint64_t inst_begin, uint64_t inst_count, uint32_t key_cap,
+                            const bftsim_audit_out *out, bftsim_audit_report *report);
+/* diagnostics: device times (ms, HIP events) of the last audit's decode kernel, recoveries, classification + tally, and
+ * copies (the stream to the device, the outputs back), as scripts/audit_bench.py records them */
+int bftsim_audit_last_ms(bftsim_t *h, float *decode_ms, float *recover_ms, float *tally_ms, float *copy_ms);
+
 /* ValidatorSet / block helpers on the host (validator.rs, types/block.rs) */
 uint32_t bftsim_two_thirds_majority(uint32_t n);                    /* validator.rs:149-154 */
 uint32_t bftsim_seed_from_hash(const uint8_t hash[32], uint32_t n); /* validator.rs:39-48 (BE) */
