@@ -82,16 +82,13 @@ struct Params {
     uint32_t* sfx;                    // [n_inst][sfx_rows][SFX_DWORDS]
     uint32_t sfx_x0, sfx_rows;
     uint32_t chain_prio;              // s_setprio of the block-hash chain waves (0..3)
-    uint32_t fast_lds_pad;            // A/B arms only (BFTSIM_TESTING + BFTSIM_FAST_LDS_PAD): extra LDS per FAST wave
     uint32_t rcs_k;                   // RoundChangeSet rounds per validator (bftsim_set_rcs_capacity)
-    uint32_t pad5;
     // little-endian seeds, N = 64: the predicted canonical blocks (bft_seed_chain_kernel; nullptr: none)
     uint32_t* spec;                   // [heights + 1][n_inst] spec_word or 0
     // block-hash chains (kern_fast.hip): CHAIN_RECORDED / CHAIN_PREDICTED / CHAIN_REPAIR (bft_hip.h)
     uint32_t chain_mode;
     uint32_t chain_grid;              // lane-chain kernel: at most this many (persistent) waves; 0: one per task
     uint32_t chain_inline;            // lane-chain kernel: each lane encodes its suffixes (no suffix rows)
-    uint32_t fast_prio;               // s_setprio of the FAST kernel + 1 (0: its default, 2; BFTSIM_FAST_PRIO)
 };
 constexpr uint32_t RCS_DEFAULT_K = 16, RCS_MAX_K = 4096;
 // one logged broadcast: {tick, phase | code << 8 | sender << 16, height, round, block id lo, hi,

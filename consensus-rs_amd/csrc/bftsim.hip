@@ -400,18 +400,8 @@ __global__ __launch_bounds__(256) void bft_trace_meta_kernel(TraceArgs a, uint64
     const uint32_t* e = a.mlog + ref * MLOG_WORDS;
     ((uint4*)meta)[m - m0] = make_uint4(e[0], e[1], e[6], (uint32_t)(ref / a.cap) - inst_begin);
 }
-// emit pass, the serial shape (lane per frame, byte stores to global memory): the first correct version, kept
-// as the A/B baseline (BFTSIM_TESTING + BFTSIM_TRACE_SERIAL=1). `out` holds the frames of [m0, m1).
-__global__ __launch_bounds__(64) void bft_trace_emit_serial_kernel(Params p, TraceArgs a, uint64_t m0, uint64_t m1,
-                                                                   const uint64_t* foff, uint8_t* out, uint32_t* err) {
-    __shared__ __attribute__((aligned(16))) uint8_t hb[64 * LANE_HASH_BUF];
-    const uint64_t m = m0 + (uint64_t)blockIdx.x * 64u + threadIdx.x;
-    if (m >= m1) return;
-    const uint32_t len = (uint32_t)(foff[m + 1] - foff[m]);
-    if (trace::write_frame(out + (foff[m] - foff[m0]), len, trace_msg(p, a, m, hb + threadIdx.x * LANE_HASH_BUF)) != len)
-        atomicAdd(err, 1u);
-}
-// emit pass: a wave per 64 consecutive frames, which are one contiguous piece of the stream. Each lane expands
+// emit pass (`out` holds the frames of [m0, m1)): a wave per 64 consecutive frames, which are one contiguous piece
+// of the stream. Each lane expands
 // its frame into an LDS stage laid out like that piece (as many whole frames per round as the stage holds), then
 // the wave copies the stage out with coalesced 16-byte stores (byte stores for the unaligned head and tail).
 // Every lane's writes are bounded by its frame's counted length and the copy by the counted lengths of the
@@ -533,7 +523,6 @@ struct bftsim {
     void* sig = nullptr;              // libbftsig handle (bftsig_t*)
     // the trace (bftsim_set_trace_keep, SPEC.md §11b): what bftsim_crypto_verify kept of the last launch
     bool trace_keep = false;
-    bool testing = false;             // BFTSIM_TESTING=1 at the last prepare: the A/B switches below are read at all
     uint8_t* d_tkeep = nullptr;       // one allocation: moff, mref, raw, msg_k, sigs, seals (trace_args points into it)
     bft::TraceArgs trace_args{};
     uint64_t trace_n = 0, trace_M = 0;    // instances (0: nothing kept) and messages it holds
@@ -602,15 +591,12 @@ struct bftsim {
     // streams (0.3-0.45 ms per cfg3 launch beside the FAST kernels), no 400 MB of rows written and read back
     // (BFTSIM_TESTING + BFTSIM_CHAIN_INLINE=0: the suffix rows)
     uint32_t chain_inline = 1;
-    uint32_t chain_prio = 0;          // s_setprio of the chain waves (BFTSIM_TESTING + BFTSIM_CHAIN_PRIO)
-    // predicted chains (small shards, their latency the step's tail): above the FAST kernels' 2, with their suffix
-    // rows (2,048 per GPU: 1.08e9 at 0, 1.13e9-1.22e9 at 3; profiles/r06/ab_prio; BFTSIM_CHAIN_PRIO_SPEC)
-    uint32_t chain_prio_spec = 3;
-    // predicted LANE chains (large shards: throughput, not latency) below the FAST kernels: 2.06e9-2.10e9 at 0 or 1
-    // against 1.80e9-1.93e9 at 3 (cfg3; profiles/r06/ab_spec_lane; BFTSIM_CHAIN_PRIO_SPEC_LANE)
-    uint32_t chain_prio_spec_lane = 0;
-    uint32_t chain_prio_spec_early = 3;   // A/B: BFTSIM_CHAIN_PRIO_SPEC_EARLY
-    uint32_t fast_lds_pad = 0;        // extra LDS per FAST wave: fewer resident FAST waves (BFTSIM_TESTING + BFTSIM_FAST_LDS_PAD)
+    // s_setprio of the chain waves (Params::chain_prio), against the FAST kernels' 2. Recorded chains: 0. Predicted
+    // lane pairs (small shards, their latency the step's tail) above the FAST kernels, with their suffix rows, at the
+    // sync's flush and at earlier ones alike: 2,048 per GPU 1.08e9 at 0, 1.13e9-1.22e9 at 3 (profiles/r06/ab_prio).
+    // Predicted lanes (large shards: throughput, not latency) below them: cfg3 2.06e9-2.10e9 at 0 or 1 against
+    // 1.80e9-1.93e9 at 3 (profiles/r06/ab_spec_lane).
+    static constexpr uint32_t PRIO_RECORDED = 0, PRIO_SPEC_PAIR = 3, PRIO_SPEC_LANE = 0;
     bool seed_spec = true;            // little-endian seeds, N = 64: predicted blocks (BFTSIM_TESTING + BFTSIM_SEED_SPEC=0: off)
     int pipeline = 0;                 // number of row-table sets (0: no pipelining)
     uint32_t sfx_rows = 0;            // heights per hash-pass chunk (0: no hash pass)
@@ -620,10 +606,10 @@ struct bftsim {
     uint32_t n_cs = 2, n_hs = 2, cur_cs = 0, cur_hs = 0;
     // launch streams with little-endian seeds: a launch's seed chain and FAST kernel are serial on its stream
     // and there is no hash pass, so more launches run side by side (profiles/r04/ab_le_streams)
-    uint32_t n_cs_seeded = 4;
+    static constexpr uint32_t N_CS_SEEDED = 4;
     uint32_t hash_batch = 4;          // launches per chain kernel (BFTSIM_TESTING + BFTSIM_HASH_BATCH overrides)
     // big-endian seeds, N = 64, pipelined: the chains of a batch run on predicted blocks from launch time on
-    // (BFTSIM_TESTING + BFTSIM_HASH_SPEC=0: off), over up to n_hs_spec hash streams so that the
+    // (BFTSIM_TESTING + BFTSIM_HASH_SPEC=0: off), over up to N_HS_SPEC hash streams so that the
     // batches of a burst of launches run side by side
     // on at every size: a small shard's chains (lane pairs) are bound by their latency, which they start ahead
     // of; a large shard's (lanes, each predicting and encoding its blocks itself) fill the issue slots the consensus
@@ -632,31 +618,19 @@ struct bftsim {
     // for lossy schedules too
     uint64_t hash_spec_max = ~0ull;
     bool spec_lossy = false;          // predicted chains with drops or crashes too (BFTSIM_HASH_SPEC=2)
-    uint32_t n_hs_spec = 3;
+    static constexpr uint32_t N_HS_SPEC = 3;
     struct Pending { uint32_t set, ev, first, cs; } pend[MAX_BATCH];   // cs: the launch stream it ran on
-    // one event per chain batch (flush_batch) instead of one per set: a ring, re-recorded after BATCH_EVS batches (a set
-    // still pointing at a re-recorded event waits for a later batch: later, never wrong)
+    // one event per chain batch (flush_batch) instead of one per set: a ring, re-recorded after BATCH_EVS batches. Safe
+    // because BATCH_EVS > MAX_SETS: a batch marks at least one set, so more than MAX_SETS batches cannot all still be
+    // some set's batch_done; by the time an event is re-recorded no set points at it
     static constexpr uint32_t BATCH_EVS = 64;
+    static_assert(BATCH_EVS > MAX_SETS, "a re-recorded batch event must not be any set's batch_done");
     hipEvent_t batch_ev[BATCH_EVS] = {};
     uint32_t batch_ev_head = 0;
     uint32_t n_pend = 0;
     bft::Params batch_p{};            // the launch parameters of the pending batch (sizes, genesis, prio)
     bool batch_spec = false;          // the pending batch runs predicted chains
     uint32_t batch_hs = 0;            // the pending batch's hash stream (chosen at its first launch)
-    // predicted suffix rows per launch at the launch, on the batch's hash stream (0: the whole batch's at the flush;
-    // BFTSIM_TESTING + BFTSIM_SPEC_EARLY)
-    uint32_t spec_early = 0;
-    uint32_t rec_clear = 0;           // zero the record rows of FAST launches too (BFTSIM_TESTING + BFTSIM_REC_CLEAR)
-    uint32_t diag_no_chain = 0;       // diagnostic: flush_batch enqueues no chain kernels (wrong hashes)
-    uint32_t diag_no_clear = 0;       // diagnostic: no bft_clear_kernel (wrong statistics, hand-overs)
-    uint32_t fast_prio = 0;           // FAST kernel priority + 1 (0: the kernel's default; BFTSIM_FAST_PRIO)
-    uint32_t first_batch = 0;         // launches in the first chain batch after a sync (0: hash_batch; BFTSIM_FIRST_BATCH)
-    uint32_t conv_stream = 0;         // a converted final batch on a hash stream of its own (A/B: BFTSIM_CONV_STREAM;
-                                      // 1.70e9-1.74e9 against 1.82e9-1.85e9 on the batch's, profiles/r06/ab_conv_stream)
-    uint32_t chain_on_launch = 0;     // the chain batches on the last launch's stream (BFTSIM_CHAIN_ON_LAUNCH)
-    uint32_t spec_final = 1;
-    uint32_t spec_first = 0;          // the first batch after a sync as predicted pair chains too (BFTSIM_SPEC_FIRST)
-    bool synced = true, batch_after_sync = false;          // the flush of bftsim_sync as predicted pair chains (BFTSIM_TESTING + BFTSIM_SPEC_FINAL)   // measured: 0.99e9-1.07e9 early vs 1.09e9-1.13e9 at the flush (profiles/r06/ab_spec_early)
     // per-launch kernel timing: a ring of event quadruples, read by bftsim_kernel_ms_sum
     static constexpr uint32_t RING = 64;
     struct LaunchEv { hipEvent_t c0, c1, h0, h1, sx; bool has_hash, pending; } ring[RING] = {};
@@ -674,6 +648,36 @@ static int fail(bftsim* h, int code, const std::string& msg) {
         hipError_t e_ = (x);                                                                    \
         if (e_ != hipSuccess) return fail(h, BFTSIM_EHIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
     } while (0)
+
+// Owners of the cold paths' temporaries (verify, export, audit): released on every return, so that each HIP call
+// there is a HIPCHECK with an early return. Not for the launch path, which owns nothing temporary.
+namespace {                           // internal: the library exports none of their members
+struct DevMem {                       // a device allocation
+    void* p = nullptr;
+    DevMem() = default;
+    DevMem(DevMem&& o) noexcept : p(o.release<void>()) {}
+    DevMem(const DevMem&) = delete;
+    DevMem& operator=(const DevMem&) = delete;
+    ~DevMem() { (void)hipFree(p); }
+    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes); }
+    template <class T> T* as() const { return (T*)p; }
+    template <class T> T* release() { T* r = (T*)p; p = nullptr; return r; }   // the handle takes the allocation over
+};
+struct Events {                       // up to MAX timing events
+    static constexpr int MAX = 5;
+    hipEvent_t ev[MAX] = {};
+    Events() = default;
+    Events(const Events&) = delete;
+    Events& operator=(const Events&) = delete;
+    ~Events() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+    hipError_t create(int n) {
+        for (int k = 0; k < n && k < MAX; ++k)
+            if (hipError_t e = hipEventCreate(&ev[k]); e != hipSuccess) return e;
+        return hipSuccess;
+    }
+    hipEvent_t operator[](int k) const { return ev[k]; }
+};
+}  // namespace
 
 // the attribution pass's eviction after a kernel (a no-op unless BFTSIM_TESTING=1 and BFTSIM_PMC_EVICT=1)
 static constexpr uint64_t EVICT_BYTES = 64ull << 20;
@@ -756,7 +760,6 @@ static int flush_batch(bftsim* h, bool final = false);
 static int sync_all(bftsim* h) {
     HIPCHECK(h, hipSetDevice(h->device));
     if (int rc = flush_batch(h, true)) return rc;
-    h->synced = true;
     HIPCHECK(h, hipStreamSynchronize(h->last_stream));
     for (uint32_t k = 0; k < bftsim::MAX_CS; ++k)
         if (h->cs[k]) HIPCHECK(h, hipStreamSynchronize(h->cs[k]));
@@ -1014,49 +1017,41 @@ int bftsim_prepare(bftsim_t* h, uint64_t n) {
     h->sets[0].hist = h->d_hist; h->sets[0].rcs = h->d_rcs; h->sets[0].backlog = h->d_backlog;
     h->sets[0].resume = h->d_resume; h->sets[0].save = h->d_save; h->sets[0].resume_q = h->d_resume_q;
     h->n_sets = 1;
+    // the switches of the tests and the A/B scripts, read only under BFTSIM_TESTING=1 (never the product path): a
+    // 32-bit one clamped to [lo, hi], a 64-bit one as written; both say whether the variable was set
+    const char* tst = getenv("BFTSIM_TESTING");
+    const bool testing = tst && strcmp(tst, "1") == 0;
+    auto knob = [&](const char* name, uint32_t& v, uint32_t lo, uint32_t hi) {
+        const char* e = getenv(name);
+        if (!testing || !e) return false;
+        const uint32_t x = (uint32_t)atoi(e);
+        v = x < lo ? lo : x > hi ? hi : x;
+        return true;
+    };
+    auto knob64 = [&](const char* name, uint64_t& v) {
+        const char* e = getenv(name);
+        if (!testing || !e) return false;
+        v = strtoull(e, nullptr, 10);
+        return true;
+    };
+    uint32_t sfx_cap = 0;             // fewer heights per suffix-row chunk, so that small batches take the chunked path
     {
-        const char* tst = getenv("BFTSIM_TESTING");
-        const bool testing = tst && strcmp(tst, "1") == 0;
-        h->testing = testing;
-        const char* cw = getenv("BFTSIM_CHAIN_WAVE_MAX");
-        if (testing && cw) h->chain_wave_max = strtoull(cw, nullptr, 10);
-        const char* cl = getenv("BFTSIM_CHAIN_LANE_MIN");
-        if (testing && cl) h->chain_lane_min = strtoull(cl, nullptr, 10);
-        const char* cp = getenv("BFTSIM_CHAIN_PRIO");
-        if (testing && cp) h->chain_prio = (uint32_t)atoi(cp);
-        const char* lp = getenv("BFTSIM_FAST_LDS_PAD");
-        if (testing && lp) h->fast_lds_pad = (uint32_t)atoi(lp) > 60000u ? 60000u : (uint32_t)atoi(lp);
-        auto knob = [&](const char* name, uint32_t& v, uint32_t lo, uint32_t hi) {
-            const char* e = getenv(name);
-            if (testing && e) { const uint32_t x = (uint32_t)atoi(e); v = x < lo ? lo : x > hi ? hi : x; }
-        };
+        knob64("BFTSIM_CHAIN_WAVE_MAX", h->chain_wave_max);
+        knob64("BFTSIM_CHAIN_LANE_MIN", h->chain_lane_min);
         knob("BFTSIM_LAUNCH_STREAMS", h->n_cs, 1, bftsim::MAX_CS);
         knob("BFTSIM_CHAIN_GRID", h->chain_grid, 0, 1u << 20);
-        knob("BFTSIM_CHAIN_PRIO_SPEC", h->chain_prio_spec, 0, 3);
-        knob("BFTSIM_CHAIN_PRIO_SPEC_LANE", h->chain_prio_spec_lane, 0, 3);
-        knob("BFTSIM_CHAIN_PRIO_SPEC_EARLY", h->chain_prio_spec_early, 0, 3);
-        knob("BFTSIM_SPEC_EARLY", h->spec_early, 0, 1);
-        knob("BFTSIM_SPEC_FINAL", h->spec_final, 0, 1);
-        knob("BFTSIM_SPEC_FIRST", h->spec_first, 0, 1);
-        knob("BFTSIM_REC_CLEAR", h->rec_clear, 0, 1);
-        knob("BFTSIM_DIAG_NO_CHAIN", h->diag_no_chain, 0, 1);
-        knob("BFTSIM_DIAG_NO_CLEAR", h->diag_no_clear, 0, 1);
-        knob("BFTSIM_CONV_STREAM", h->conv_stream, 0, 1);
-        knob("BFTSIM_FIRST_BATCH", h->first_batch, 0, bftsim::MAX_BATCH);
-        knob("BFTSIM_FAST_PRIO", h->fast_prio, 0, 4);
-        knob("BFTSIM_CHAIN_ON_LAUNCH", h->chain_on_launch, 0, 1);
         knob("BFTSIM_CHAIN_INLINE", h->chain_inline, 0, 1);
-        knob("BFTSIM_LAUNCH_STREAMS_SEEDED", h->n_cs_seeded, 1, bftsim::MAX_CS);
-        knob("BFTSIM_HASH_STREAMS", h->n_hs, 1, bftsim::MAX_HS);   // A/B arms
-        knob("BFTSIM_HASH_BATCH", h->hash_batch, 1, bftsim::MAX_BATCH);   // A/B arms (bftsim_set_hash_batch)
-        knob("BFTSIM_HASH_STREAMS_SPEC", h->n_hs_spec, 1, bftsim::MAX_HS);
-        const char* ss = getenv("BFTSIM_SEED_SPEC");
-        if (testing && ss) h->seed_spec = atoi(ss) != 0;
-        const char* hs = getenv("BFTSIM_HASH_SPEC");   // 0: off, 1: at every size
-        if (testing && hs) h->hash_spec_max = atoi(hs) != 0 ? ~0ull : 0ull;
-        h->spec_lossy = testing && hs && atoi(hs) == 2;   // 2: lossy schedules too (the tests of the repairs)
-        const char* pe = getenv("BFTSIM_PMC_EVICT");
-        h->pmc_evict = testing && pe && atoi(pe) != 0;   // scripts/gpu_profile.sh's attribution pass
+        knob("BFTSIM_HASH_STREAMS", h->n_hs, 1, bftsim::MAX_HS);
+        knob("BFTSIM_HASH_BATCH", h->hash_batch, 1, bftsim::MAX_BATCH);   // (bftsim_set_hash_batch)
+        knob("BFTSIM_SFX_ROWS", sfx_cap, 0, 0x7fffffffu);
+        uint32_t ss = h->seed_spec, hs = 0, pe = 0;
+        knob("BFTSIM_SEED_SPEC", ss, 0, 1);
+        h->seed_spec = ss != 0;
+        // 0: off, any other value: at every size; 2: lossy schedules too (the tests of the repairs)
+        if (knob("BFTSIM_HASH_SPEC", hs, 0, ~0u)) h->hash_spec_max = hs ? ~0ull : 0ull;
+        h->spec_lossy = hs == 2;
+        knob("BFTSIM_PMC_EVICT", pe, 0, 1);            // scripts/gpu_profile.sh's attribution pass
+        h->pmc_evict = pe != 0;
         if (h->pmc_evict && !h->d_evict) {          // before any launch, so every eviction is the same dispatch
             HIPCHECK(h, hipMalloc(&h->d_evict, EVICT_BYTES + 16));
             HIPCHECK(h, hipMemset(h->d_evict, 0, EVICT_BYTES + 16));
@@ -1091,10 +1086,7 @@ int bftsim_prepare(bftsim_t* h, uint64_t n) {
         uint64_t rows = (2ull << 30) / per_row;
         if (rows < 1) rows = 1;
         if (rows > h->cfg.heights) rows = h->cfg.heights;
-        // tests only (BFTSIM_TESTING=1): fewer heights per chunk, so that small batches take the chunked path
-        const char* tst = getenv("BFTSIM_TESTING");
-        const char* cap = getenv("BFTSIM_SFX_ROWS");
-        if (tst && cap && strcmp(tst, "1") == 0 && atoi(cap) > 0 && (uint64_t)atoi(cap) < rows) rows = (uint64_t)atoi(cap);
+        if (sfx_cap > 0 && sfx_cap < rows) rows = sfx_cap;   // tests only (BFTSIM_SFX_ROWS)
         if (rows * n >= (1ull << 32)) rows = ((1ull << 32) - 1) / n;
         h->sfx_rows = (uint32_t)rows;
         for (uint32_t k = 0; k < h->n_sets; ++k) HIPCHECK(h, hipMalloc(&h->sets[k].sfx, rows * per_row));
@@ -1109,7 +1101,7 @@ int bftsim_prepare(bftsim_t* h, uint64_t n) {
         if (h->n_sets >= 2) {
             for (uint32_t k = 0; k < h->n_cs && k < bftsim::MAX_CS; ++k)
                 if (!h->cs[k]) HIPCHECK(h, hipStreamCreateWithFlags(&h->cs[k], hipStreamNonBlocking));
-            const uint32_t nh = h->n_hs > h->n_hs_spec ? h->n_hs : h->n_hs_spec;
+            const uint32_t nh = h->n_hs > bftsim::N_HS_SPEC ? h->n_hs : bftsim::N_HS_SPEC;
             for (uint32_t k = 0; k < nh && k < bftsim::MAX_HS; ++k)
                 if (!h->hstr[k]) HIPCHECK(h, hipStreamCreateWithFlags(&h->hstr[k], hipStreamNonBlocking));
         }
@@ -1175,11 +1167,9 @@ static bft::Params make_params(bftsim* h, uint64_t first, uint64_t n) {
     p.hist = h->d_hist;
     p.rcs = h->d_rcs;
     p.rcs_k = h->rcs_k;
-    p.chain_prio = h->chain_prio;
-    p.fast_prio = h->fast_prio;
+    p.chain_prio = bftsim::PRIO_RECORDED;
     p.chain_grid = h->chain_grid;
     p.chain_inline = h->chain_inline;
-    p.fast_lds_pad = h->fast_lds_pad;
     p.backlog = h->d_backlog;
     if (h->crypto && h->d_mlog) {
         p.mlog = h->d_mlog;
@@ -1267,7 +1257,7 @@ int bftsim_launch(bftsim_t* h, uint64_t first, void* stream) {
         bftsim::RowSet& r = h->sets[h->cur_set];
         if (!r.entry) HIPCHECK(h, hipEventCreateWithFlags(&r.entry, hipEventDisableTiming));
         HIPCHECK(h, hipEventRecord(r.entry, s));
-        h->cur_cs = (h->cur_cs + 1) % (spec ? h->n_cs_seeded : h->n_cs);
+        h->cur_cs = (h->cur_cs + 1) % (spec ? bftsim::N_CS_SEEDED : h->n_cs);
         if (!h->cs[h->cur_cs]) HIPCHECK(h, hipStreamCreateWithFlags(&h->cs[h->cur_cs], hipStreamNonBlocking));
         hipStream_t ls = h->cs[h->cur_cs];
         HIPCHECK(h, hipStreamWaitEvent(ls, r.entry, 0));
@@ -1296,15 +1286,13 @@ int bftsim_launch(bftsim_t* h, uint64_t first, void* stream) {
     // except for FAST launches: the FAST and resume bodies read a row only once they have recorded it (canon_blk,
     // canon_seed, refresh_tip_from_table: rows <= the canonical height), and every reader after the launch stops at
     // the committed height (fetch, export, tips, chains, the predicted chains' check) -- 43 MB of writes per cfg3
-    // launch saved (BFTSIM_TESTING + BFTSIM_REC_CLEAR=1: cleared anyway)
-    const bool clear_rec = !fast_launch || h->rec_clear;
+    // launch saved
+    const bool clear_rec = !fast_launch;
     const uint64_t n_rec = clear_rec ? (uint64_t)n * h->hcap : 0;
-    if (!h->diag_no_clear) {   // (diagnostic BFTSIM_DIAG_NO_CLEAR=1: the host cost of this dispatch; wrong statistics)
-        hipLaunchKernelGGL(bft_clear_kernel, dim3(clear_blocks(n_rec > n ? n_rec : n)), dim3(256), 0, s, (uint4*)h->d_rec,
-                           n_rec, h->d_hist, fast_launch ? h->d_resume : nullptr, (uint32_t)n,
-                           fast_launch ? h->d_resume_q : nullptr);
-        HIPCHECK(h, hipGetLastError());
-    }
+    hipLaunchKernelGGL(bft_clear_kernel, dim3(clear_blocks(n_rec > n ? n_rec : n)), dim3(256), 0, s, (uint4*)h->d_rec,
+                       n_rec, h->d_hist, fast_launch ? h->d_resume : nullptr, (uint32_t)n,
+                       fast_launch ? h->d_resume_q : nullptr);
+    HIPCHECK(h, hipGetLastError());
     if (h->d_backlog) HIPCHECK(h, hipMemsetAsync(h->d_backlog, 0, h->backlog_bytes, s));
     uint32_t per_block = h->seg > 64 ? 1u : 64u / h->seg;      // instances per workgroup
     uint32_t grid = (uint32_t)((n + per_block - 1) / per_block);
@@ -1376,31 +1364,12 @@ int bftsim_launch(bftsim_t* h, uint64_t first, void* stream) {
             if (h->n_pend == 0) {
                 h->batch_p = p;
                 h->batch_spec = hspec;
-                h->batch_after_sync = h->synced;
-                h->synced = false;
-                h->cur_hs = (h->cur_hs + 1) % (hspec ? h->n_hs_spec : h->n_hs);   // the batch's hash stream
+                h->cur_hs = (h->cur_hs + 1) % (hspec ? bftsim::N_HS_SPEC : h->n_hs);   // the batch's hash stream
                 if (!h->hstr[h->cur_hs]) HIPCHECK(h, hipStreamCreateWithFlags(&h->hstr[h->cur_hs], hipStreamNonBlocking));
                 h->batch_hs = h->cur_hs;
             }
-            if (hspec && h->spec_early) {
-                // this launch's predicted suffix rows now, on the batch's hash stream, once its set is free (the
-                // caller's earlier work, the set's last hash pass): at the flush only the chains are left
-                hipStream_t t = h->hstr[h->batch_hs];
-                HIPCHECK(h, hipStreamWaitEvent(t, r.entry, 0));
-                if (r.busy) HIPCHECK(h, hipStreamWaitEvent(t, r.batch_done ? r.batch_done : r.done, 0));
-                bft::ChainSets one{};
-                one.count = 1;
-                one.sfx[0] = r.sfx; one.byz[0] = r.byz; one.bad[0] = r.bad; one.pred[0] = r.pred;
-                one.first[0] = (uint32_t)first;
-                bft::Params ps = p;
-                ps.chain_prio = h->chain_prio_spec;
-                HIPCHECK(h, bft::launch_spec_suffix((uint32_t)n, one, t, ps));
-                HIPCHECK(h, pmc_evict(h, t));
-            }
             h->pend[h->n_pend++] = {h->cur_set, (h->ring_head - 1) % bftsim::RING, (uint32_t)first, h->cur_cs};
-            // the burst's first batch may be shorter (its chains start sooner; A/B: BFTSIM_FIRST_BATCH)
-            const uint32_t cap = h->batch_after_sync && h->first_batch ? h->first_batch : h->hash_batch;
-            if (h->n_pend >= cap) if (int rc = flush_batch(h)) return rc;
+            if (h->n_pend >= h->hash_batch) if (int rc = flush_batch(h)) return rc;
         } else {
             // one launch's hash pass: on a hash stream (pipelined) or the launch stream; chunks of K heights
             // share the suffix rows (suffix and chain kernels in order on one stream)
@@ -1451,17 +1420,9 @@ static int flush_batch(bftsim* h, bool final) {
     // start once the last launch's consensus kernel is done and take ~2 ms) runs as predicted lane-pair chains
     // instead: they start now, beside the launches' consensus kernels, and only the check and the repairs are left
     // behind them. With predictions on (the default) every batch is predicted already (§4j).
-    const bool first = h->batch_after_sync && h->spec_first;   // the burst's first batch (A/B arm)
-    const bool conv = ((final && h->spec_final) || first) && !h->batch_spec && h->sets[h->pend[0].set].byz != nullptr &&
+    const bool conv = final && !h->batch_spec && h->sets[h->pend[0].set].byz != nullptr &&
                       ((h->batch_p.thr16 == 0 && h->batch_p.crash_on == 0) || h->spec_lossy);   // lossless (launch)
     const bool spec = h->batch_spec || conv;
-    if (h->chain_on_launch) t = h->cs[h->pend[h->n_pend - 1].cs];   // A/B: behind the launches, no overlap
-    else if (conv && h->conv_stream && h->n_hs < bftsim::MAX_HS) {
-        // on a hash stream of its own: on the batch's (recorded chains' rotation) it would start only behind the
-        // recorded chains of an earlier batch there, ~9 ms at 16,384 (profiles/r06/traces/r06af_timeline_t16k.txt)
-        if (!h->hstr[h->n_hs]) HIPCHECK(h, hipStreamCreateWithFlags(&h->hstr[h->n_hs], hipStreamNonBlocking));
-        t = h->hstr[h->n_hs];
-    }
     bft::ChainSets cs{};
     cs.count = h->n_pend;
     // a launch stream runs its launches in order, so the last pending launch of each launch stream stands for the
@@ -1473,7 +1434,7 @@ static int flush_batch(bftsim* h, bool final) {
     if (!spec) {
         for (uint32_t k = 0; k < bftsim::MAX_CS; ++k)
             if (last_on[k] >= 0) HIPCHECK(h, hipStreamWaitEvent(t, h->ring[h->pend[last_on[k]].ev].sx, 0));
-    } else if (!h->spec_early || conv) {
+    } else {
         // predicted chains need only their sets free, not the launch streams' earlier kernels: the caller's work
         // before the last pending launch (its entry event: the caller's stream is in order) and each distinct
         // previous hash pass of the sets
@@ -1499,23 +1460,16 @@ static int flush_batch(bftsim* h, bool final) {
     bftsim::LaunchEv& last = h->ring[h->pend[h->n_pend - 1].ev];
     bft::Params p = h->batch_p;
     HIPCHECK(h, hipEventRecord(last.h0, t));
-    if (h->diag_no_chain) {
-        // diagnostic (BFTSIM_TESTING + BFTSIM_DIAG_NO_CHAIN=1): no chain kernels, so no block hashes; the consensus
-        // kernels' pace alone
-    } else if (spec) {
-        // a converted final batch on lane pairs (its chains are the burst's tail: latency); the burst's first batch
-        // (spec_first) has the whole burst to finish in, so it keeps the large shard's lanes (throughput)
-        const uint32_t kind = conv && !(first && !final) ? bft::CHAIN_KERNEL_PAIR : chain_kind(h, p.n_instances, true);
-        // lane pairs: the sync's batch (the burst's tail) at chain_prio_spec, earlier full batches (slack: they end
-        // long before the burst does) at chain_prio_spec_early
-        p.chain_prio = kind == bft::CHAIN_KERNEL_LANE ? h->chain_prio_spec_lane
-                     : final ? h->chain_prio_spec : h->chain_prio_spec_early;
+    if (spec) {
+        // a converted final batch on lane pairs (its chains are the burst's tail: latency)
+        const uint32_t kind = conv ? bft::CHAIN_KERNEL_PAIR : chain_kind(h, p.n_instances, true);
+        p.chain_prio = kind == bft::CHAIN_KERNEL_LANE ? bftsim::PRIO_SPEC_LANE : bftsim::PRIO_SPEC_PAIR;
         // the predicted blocks' suffix rows and chains, which need nothing of the consensus kernels (one suffix
         // pass for the whole batch: per launch on a stream of their own they fell behind the launches); once
         // every launch's consensus kernel is done, the check of its recorded blocks against the predictions, and
         // the chains again from the first height that differs
         // (inline lane chains predict, mask and encode each block themselves: no suffix pass)
-        if ((!h->spec_early || conv) && !(kind == bft::CHAIN_KERNEL_LANE && h->chain_inline)) {
+        if (!(kind == bft::CHAIN_KERNEL_LANE && h->chain_inline)) {
             HIPCHECK(h, bft::launch_spec_suffix(p.n_instances, cs, t, p));
             HIPCHECK(h, pmc_evict(h, t));
         }
@@ -1670,19 +1624,15 @@ int bftsim_export_headers(bftsim_t* h, uint64_t capacity, uint8_t* hdr, uint32_t
     if (int rc = sync_all(h)) return rc;
     const uint64_t n = h->last_n, H = h->cfg.heights, cnt = n * H;
     bft::Params p = make_params(h, h->last_first, n);
-    uint8_t* d_out = nullptr;
-    uint32_t* d_len = nullptr;
-    HIPCHECK(h, hipMalloc(&d_out, cnt * BFTSIM_HEADER_SLOT));
-    HIPCHECK(h, hipMalloc(&d_len, cnt * 4));
+    DevMem d_out, d_len;
+    HIPCHECK(h, d_out.alloc(cnt * BFTSIM_HEADER_SLOT));
+    HIPCHECK(h, d_len.alloc(cnt * 4));
     hipLaunchKernelGGL(bft::bft_export_kernel, dim3((uint32_t)((cnt + 255) / 256)), dim3(256), 0, h->last_stream, p,
-                       d_out, d_len);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(h->last_stream);
-    if (e == hipSuccess) e = hipMemcpy(hdr, d_out, cnt * BFTSIM_HEADER_SLOT, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(hdr_len, d_len, cnt * 4, hipMemcpyDeviceToHost);
-    (void)hipFree(d_out);
-    (void)hipFree(d_len);
-    if (e != hipSuccess) return fail(h, BFTSIM_EHIP, std::string("bftsim_export_headers: ") + hipGetErrorString(e));
+                       d_out.as<uint8_t>(), d_len.as<uint32_t>());
+    HIPCHECK(h, hipGetLastError());
+    HIPCHECK(h, hipStreamSynchronize(h->last_stream));
+    HIPCHECK(h, hipMemcpy(hdr, d_out.p, cnt * BFTSIM_HEADER_SLOT, hipMemcpyDeviceToHost));
+    HIPCHECK(h, hipMemcpy(hdr_len, d_len.p, cnt * 4, hipMemcpyDeviceToHost));
     return BFTSIM_OK;
 }
 
@@ -1822,17 +1772,15 @@ int bftsim_set_crypto(bftsim_t* h, const uint8_t* secrets32, const uint8_t* forg
     if (!h->d_keys) HIPCHECK(h, hipMalloc(&h->d_keys, (size_t)2 * 256 * 32));
     HIPCHECK(h, hipMemcpy(h->d_keys, keys.data(), keys.size(), hipMemcpyHostToDevice));
     // every secret must derive the validator address of its index (the sorted validator set)
-    uint8_t *d_addr = nullptr, *d_ok = nullptr;
-    HIPCHECK(h, hipMalloc(&d_addr, (size_t)n * 20));
-    HIPCHECK(h, hipMalloc(&d_ok, n));
-    int rc = a.secret_to_address(h->sig, h->d_keys, n, nullptr, d_addr, d_ok, nullptr);
+    DevMem d_addr, d_ok;
+    HIPCHECK(h, d_addr.alloc((size_t)n * 20));
+    HIPCHECK(h, d_ok.alloc(n));
+    if (a.secret_to_address(h->sig, h->d_keys, n, nullptr, d_addr.as<uint8_t>(), d_ok.as<uint8_t>(), nullptr) != 0)
+        return fail(h, BFTSIM_EHIP, std::string("bftsig_secret_to_address: ") + a.last_error(h->sig));
     std::vector<uint8_t> addr((size_t)n * 20), ok(n);
-    hipError_t e = rc == 0 ? hipDeviceSynchronize() : hipSuccess;
-    if (rc == 0 && e == hipSuccess) e = hipMemcpy(addr.data(), d_addr, addr.size(), hipMemcpyDeviceToHost);
-    if (rc == 0 && e == hipSuccess) e = hipMemcpy(ok.data(), d_ok, n, hipMemcpyDeviceToHost);
-    (void)hipFree(d_addr); (void)hipFree(d_ok);
-    if (rc != 0) return fail(h, BFTSIM_EHIP, std::string("bftsig_secret_to_address: ") + a.last_error(h->sig));
-    if (e != hipSuccess) return fail(h, BFTSIM_EHIP, hipGetErrorString(e));
+    HIPCHECK(h, hipDeviceSynchronize());
+    HIPCHECK(h, hipMemcpy(addr.data(), d_addr.p, addr.size(), hipMemcpyDeviceToHost));
+    HIPCHECK(h, hipMemcpy(ok.data(), d_ok.p, n, hipMemcpyDeviceToHost));
     for (uint32_t v = 0; v < n; ++v)
         if (!ok[v] || memcmp(addr.data() + 20u * v, h->addresses.data() + 20u * v, 20) != 0)
             return fail(h, BFTSIM_EINVAL, "secret " + std::to_string(v) + " does not derive validator address " +
@@ -1879,15 +1827,12 @@ int bftsim_crypto_verify(bftsim_t* h, bftsim_crypto_report* out, uint64_t capaci
     trace_drop(h);
     const bool keep = h->trace_keep;
     if (keep) off.push_back(M);
-    uint8_t *pool = nullptr, *kpool = nullptr;
-    if (keep) HIPCHECK(h, hipMalloc(&kpool, (n + 1) * 8 + Mx * (8 + 32 + 4 + 65 + 65) + 6 * 16));
+    DevMem pool, kpool;
+    if (keep) HIPCHECK(h, kpool.alloc((n + 1) * 8 + Mx * (8 + 32 + 4 + 65 + 65) + 6 * 16));
     // with keep on the six kept arrays (182 B per message) are not in the temporary pool
     const uint64_t bytes = n * 8 + Mx * (sz_msg + sz_cm - (keep ? 8 + 32 + 4 + 65 + 65 : 0)) + n * 32 + 64 + 256;
-    if (hipError_t pe = hipMalloc(&pool, bytes); pe != hipSuccess) {
-        (void)hipFree(kpool);
-        return fail(h, BFTSIM_EHIP, std::string("hipMalloc(&pool, bytes): ") + hipGetErrorString(pe));
-    }
-    uint8_t *q = pool, *kq = kpool;
+    HIPCHECK(h, pool.alloc(bytes));
+    uint8_t *q = pool.as<uint8_t>(), *kq = kpool.as<uint8_t>();
     auto take = [&](uint64_t b, bool kept = false) {
         uint8_t*& c = kept && keep ? kq : q;
         uint8_t* r = c;
@@ -1905,61 +1850,50 @@ int bftsim_crypto_verify(bftsim_t* h, bftsim_crypto_report* out, uint64_t capaci
     a.seals = take(Mx * 65, true); a.seal_ok = take(Mx); uint8_t* seal_addr = take(Mx * 20);
     uint8_t* sig_ok = take(Mx);
     a.ncm = (uint32_t*)take(4); a.inst_ck = (uint32_t*)take(n * 32); a.counts = (unsigned long long*)take(64);
-    int rc = BFTSIM_OK;
-    hipError_t e = hipMemcpyAsync(d_off, off.data(), off.size() * 8, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemsetAsync(a.ncm, 0, 4, s);
-    if (e == hipSuccess) e = hipMemsetAsync(a.inst_ck, 0, n * 32, s);
-    if (e == hipSuccess) e = hipMemsetAsync(a.counts, 0, 64, s);
+    HIPCHECK(h, hipMemcpyAsync(d_off, off.data(), off.size() * 8, hipMemcpyHostToDevice, s));
+    HIPCHECK(h, hipMemsetAsync(a.ncm, 0, 4, s));
+    HIPCHECK(h, hipMemsetAsync(a.inst_ck, 0, n * 32, s));
+    HIPCHECK(h, hipMemsetAsync(a.counts, 0, 64, s));
     bft::Params p = make_params(h, h->last_first, n);
-    uint32_t ncm = 0;
-    if (e == hipSuccess && M) {
-        hipLaunchKernelGGL(bft::bft_crypto_prep_kernel, dim3((uint32_t)n), dim3(64), 0, s, p, a);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(&ncm, a.ncm, 4, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        // commit seals first: they are part of the Commit's sign payload
-        if (e == hipSuccess && ncm && sa.sign(h->sig, h->d_keys, a.seal_key, a.seal_dig, ncm, a.seals, sig_ok, s) != 0)
-            rc = fail(h, BFTSIM_EHIP, std::string("bftsig_sign (seals): ") + sa.last_error(h->sig));
-        const uint32_t g = (uint32_t)((M + 63) / 64);
-        if (e == hipSuccess && rc == 0) {
-            hipLaunchKernelGGL(bft::bft_crypto_digest_kernel, dim3(g), dim3(64), 0, s, p, a, M);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess && rc == 0 && sa.sign(h->sig, h->d_keys, a.key, a.sign_dig, M, a.sigs, sig_ok, s) != 0)
-            rc = fail(h, BFTSIM_EHIP, std::string("bftsig_sign: ") + sa.last_error(h->sig));
-        // the receivers: recover every message's signer, and every seal (verify_commit)
-        if (e == hipSuccess && rc == 0 && sa.recover(h->sig, a.sign_dig, a.sigs, M, nullptr, a.rec_addr, a.rec_ok, s) != 0)
-            rc = fail(h, BFTSIM_EHIP, std::string("bftsig_recover: ") + sa.last_error(h->sig));
-        if (e == hipSuccess && rc == 0 && ncm &&
-            sa.recover(h->sig, a.seal_raw, a.seals, ncm, nullptr, seal_addr, a.seal_ok, s) != 0)
-            rc = fail(h, BFTSIM_EHIP, std::string("bftsig_recover (seals): ") + sa.last_error(h->sig));
-        if (e == hipSuccess && rc == 0) {
-            hipLaunchKernelGGL(bft::bft_crypto_check_kernel, dim3(g), dim3(64), 0, s, p, a, M);
-            e = hipGetLastError();
-        }
-        // the votes of every committed block, kept for bftsim_export_ledger
-        const uint64_t vs = n * (uint64_t)h->cfg.heights * h->cfg.n;
+    if (M) {
+        // the votes of the last verify go first: whatever fails below, bftsim_export_ledger finds none
         (void)hipFree(h->d_vsig); (void)hipFree(h->d_vhas);
         h->d_vsig = nullptr; h->d_vhas = nullptr; h->vsig_n = 0;
-        if (e == hipSuccess && rc == 0) e = hipMalloc(&h->d_vsig, vs * 65);
-        if (e == hipSuccess && rc == 0) e = hipMalloc(&h->d_vhas, vs);
-        if (e == hipSuccess && rc == 0) e = hipMemsetAsync(h->d_vhas, 0, vs, s);
-        if (e == hipSuccess && rc == 0) {
-            hipLaunchKernelGGL(bft::bft_crypto_votes_kernel, dim3(g), dim3(64), 0, s, p, a, M, h->d_vsig, h->d_vhas);
-            e = hipGetLastError();
-            if (e == hipSuccess) h->vsig_n = n;
-        }
+        uint32_t ncm = 0;
+        hipLaunchKernelGGL(bft::bft_crypto_prep_kernel, dim3((uint32_t)n), dim3(64), 0, s, p, a);
+        HIPCHECK(h, hipGetLastError());
+        HIPCHECK(h, hipMemcpyAsync(&ncm, a.ncm, 4, hipMemcpyDeviceToHost, s));
+        HIPCHECK(h, hipStreamSynchronize(s));
+        // commit seals first: they are part of the Commit's sign payload
+        if (ncm && sa.sign(h->sig, h->d_keys, a.seal_key, a.seal_dig, ncm, a.seals, sig_ok, s) != 0)
+            return fail(h, BFTSIM_EHIP, std::string("bftsig_sign (seals): ") + sa.last_error(h->sig));
+        const uint32_t g = (uint32_t)((M + 63) / 64);
+        hipLaunchKernelGGL(bft::bft_crypto_digest_kernel, dim3(g), dim3(64), 0, s, p, a, M);
+        HIPCHECK(h, hipGetLastError());
+        if (sa.sign(h->sig, h->d_keys, a.key, a.sign_dig, M, a.sigs, sig_ok, s) != 0)
+            return fail(h, BFTSIM_EHIP, std::string("bftsig_sign: ") + sa.last_error(h->sig));
+        // the receivers: recover every message's signer, and every seal (verify_commit)
+        if (sa.recover(h->sig, a.sign_dig, a.sigs, M, nullptr, a.rec_addr, a.rec_ok, s) != 0)
+            return fail(h, BFTSIM_EHIP, std::string("bftsig_recover: ") + sa.last_error(h->sig));
+        if (ncm && sa.recover(h->sig, a.seal_raw, a.seals, ncm, nullptr, seal_addr, a.seal_ok, s) != 0)
+            return fail(h, BFTSIM_EHIP, std::string("bftsig_recover (seals): ") + sa.last_error(h->sig));
+        hipLaunchKernelGGL(bft::bft_crypto_check_kernel, dim3(g), dim3(64), 0, s, p, a, M);
+        HIPCHECK(h, hipGetLastError());
+        // the votes of every committed block, kept for bftsim_export_ledger
+        const uint64_t vs = n * (uint64_t)h->cfg.heights * h->cfg.n;
+        HIPCHECK(h, hipMalloc(&h->d_vsig, vs * 65));
+        HIPCHECK(h, hipMalloc(&h->d_vhas, vs));
+        HIPCHECK(h, hipMemsetAsync(h->d_vhas, 0, vs, s));
+        hipLaunchKernelGGL(bft::bft_crypto_votes_kernel, dim3(g), dim3(64), 0, s, p, a, M, h->d_vsig, h->d_vhas);
+        HIPCHECK(h, hipGetLastError());
+        h->vsig_n = n;
     }
     unsigned long long c[8] = {0};
-    if (e == hipSuccess && rc == 0) e = hipMemcpyAsync(c, a.counts, 64, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && rc == 0 && inst_checksum) e = hipMemcpyAsync(inst_checksum, a.inst_ck, n * 32, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(pool);
-    if (rc || e != hipSuccess) (void)hipFree(kpool);
-    if (rc) return rc;
-    if (e != hipSuccess) return fail(h, BFTSIM_EHIP, std::string("bftsim_crypto_verify: ") + hipGetErrorString(e));
+    HIPCHECK(h, hipMemcpyAsync(c, a.counts, 64, hipMemcpyDeviceToHost, s));
+    if (inst_checksum) HIPCHECK(h, hipMemcpyAsync(inst_checksum, a.inst_ck, n * 32, hipMemcpyDeviceToHost, s));
+    HIPCHECK(h, hipStreamSynchronize(s));
     if (keep) {
-        h->d_tkeep = kpool;
+        h->d_tkeep = kpool.release<uint8_t>();
         h->trace_args = bft::TraceArgs{h->d_mlog, h->mlog_cap, a.moff, a.mref, a.raw, a.msg_k, a.sigs, a.seals};
         h->trace_n = n;
         h->trace_M = M;
@@ -1985,19 +1919,15 @@ int bftsim_export_ledger(bftsim_t* h, uint64_t capacity, uint8_t* hdr, uint64_t 
     if (int rc = sync_all(h)) return rc;
     const uint64_t n = h->last_n, H = h->cfg.heights, cnt = n * H;
     bft::Params p = make_params(h, h->last_first, n);
-    uint8_t* d_out = nullptr;
-    uint32_t* d_len = nullptr;
-    HIPCHECK(h, hipMalloc(&d_out, cnt * slot_bytes));
-    HIPCHECK(h, hipMalloc(&d_len, cnt * 4));
+    DevMem d_out, d_len;
+    HIPCHECK(h, d_out.alloc(cnt * slot_bytes));
+    HIPCHECK(h, d_len.alloc(cnt * 4));
     hipLaunchKernelGGL(bft::bft_export_votes_kernel, dim3((uint32_t)((cnt + 63) / 64)), dim3(64), 0, h->last_stream, p,
-                       h->d_vsig, h->d_vhas, d_out, slot_bytes, d_len);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(h->last_stream);
-    if (e == hipSuccess) e = hipMemcpy(hdr, d_out, cnt * slot_bytes, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(hdr_len, d_len, cnt * 4, hipMemcpyDeviceToHost);
-    (void)hipFree(d_out);
-    (void)hipFree(d_len);
-    if (e != hipSuccess) return fail(h, BFTSIM_EHIP, std::string("bftsim_export_ledger: ") + hipGetErrorString(e));
+                       h->d_vsig, h->d_vhas, d_out.as<uint8_t>(), slot_bytes, d_len.as<uint32_t>());
+    HIPCHECK(h, hipGetLastError());
+    HIPCHECK(h, hipStreamSynchronize(h->last_stream));
+    HIPCHECK(h, hipMemcpy(hdr, d_out.p, cnt * slot_bytes, hipMemcpyDeviceToHost));
+    HIPCHECK(h, hipMemcpy(hdr_len, d_len.p, cnt * 4, hipMemcpyDeviceToHost));
     return BFTSIM_OK;
 }
 
@@ -2029,43 +1959,55 @@ static int trace_size_pass(bftsim* h) {
     if (M + 1 > 0x7fffffffull) return fail(h, BFTSIM_EINVAL, "trace: too many messages for one scan");
     HIPCHECK(h, hipSetDevice(h->device));
     hipStream_t s = h->last_stream;
-    uint64_t *d = nullptr, *lens = nullptr;
-    void* tmp = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    DevMem foff, len_buf, tmp;
+    Events ev;
     size_t tb = 0;
-    hipError_t e = hipMalloc(&d, (M + 1 + n + 1) * 8 + 16);
-    if (e == hipSuccess) e = hipMalloc(&lens, (M + 1) * 8);
-    if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(nullptr, tb, lens, d, (int)(M + 1));
-    if (e == hipSuccess) e = hipMalloc(&tmp, tb ? tb : 16);
-    if (e == hipSuccess) e = hipEventCreate(&e0);
-    if (e == hipSuccess) e = hipEventCreate(&e1);
+    HIPCHECK(h, foff.alloc((M + 1 + n + 1) * 8 + 16));
+    HIPCHECK(h, len_buf.alloc((M + 1) * 8));
+    uint64_t *d = foff.as<uint64_t>(), *lens = len_buf.as<uint64_t>();
+    HIPCHECK(h, hipcub::DeviceScan::ExclusiveSum(nullptr, tb, lens, d, (int)(M + 1)));
+    HIPCHECK(h, tmp.alloc(tb ? tb : 16));
+    HIPCHECK(h, ev.create(2));
     std::vector<uint64_t> ioff(n + 1);
-    if (e == hipSuccess) {
-        bft::Params p = make_params(h, h->last_first, n);
-        e = hipEventRecord(e0, s);
-        hipLaunchKernelGGL(bft::bft_trace_size_kernel, dim3((uint32_t)((M + 1 + 63) / 64)), dim3(64), 0, s, p,
-                           h->trace_args, M, lens);
-        if (e == hipSuccess) e = hipGetLastError();
-        if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(tmp, tb, lens, d, (int)(M + 1), s);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(bft::bft_trace_inst_kernel, dim3((uint32_t)((n + 1 + 255) / 256)), dim3(256), 0, s,
-                               h->trace_args.moff, d, n + 1, d + M + 1);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipEventRecord(e1, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(ioff.data(), d + M + 1, (n + 1) * 8, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e == hipSuccess) e = hipEventElapsedTime(&h->trace_ms[0], e0, e1);
+    bft::Params p = make_params(h, h->last_first, n);
+    HIPCHECK(h, hipEventRecord(ev[0], s));
+    hipLaunchKernelGGL(bft::bft_trace_size_kernel, dim3((uint32_t)((M + 1 + 63) / 64)), dim3(64), 0, s, p,
+                       h->trace_args, M, lens);
+    HIPCHECK(h, hipGetLastError());
+    HIPCHECK(h, hipcub::DeviceScan::ExclusiveSum(tmp.p, tb, lens, d, (int)(M + 1), s));
+    hipLaunchKernelGGL(bft::bft_trace_inst_kernel, dim3((uint32_t)((n + 1 + 255) / 256)), dim3(256), 0, s,
+                       h->trace_args.moff, d, n + 1, d + M + 1);
+    HIPCHECK(h, hipGetLastError());
+    HIPCHECK(h, hipEventRecord(ev[1], s));
+    HIPCHECK(h, hipMemcpyAsync(ioff.data(), d + M + 1, (n + 1) * 8, hipMemcpyDeviceToHost, s));
+    HIPCHECK(h, hipStreamSynchronize(s));
+    HIPCHECK(h, hipEventElapsedTime(&h->trace_ms[0], ev[0], ev[1]));
+    h->d_tfoff = foff.release<uint64_t>();
+    h->trace_ioff.swap(ioff);
+    return BFTSIM_OK;
+}
+
+// emit pass: the frames of messages [m0, m1) into d_out, complete when it returns. The two passes must agree on
+// every frame's length; `what` names the caller in the error. t0 / t1 (or null): recorded around the kernel alone.
+static int trace_emit(bftsim* h, const char* what, uint64_t m0, uint64_t m1, uint8_t* d_out, hipEvent_t t0,
+                      hipEvent_t t1) {
+    hipStream_t s = h->last_stream;
+    uint32_t* d_err = (uint32_t*)(h->d_tfoff + h->trace_M + 1 + h->trace_n + 1);
+    uint32_t err = 0;
+    HIPCHECK(h, hipMemsetAsync(d_err, 0, 4, s));
+    if (t0) HIPCHECK(h, hipEventRecord(t0, s));
+    if (m1 > m0) {
+        bft::Params p = make_params(h, h->last_first, h->trace_n);
+        hipLaunchKernelGGL(bft::bft_trace_emit_kernel, dim3((uint32_t)((m1 - m0 + 63) / 64)), dim3(64), 0, s, p,
+                           h->trace_args, m0, m1, h->d_tfoff, d_out, d_err);
+        HIPCHECK(h, hipGetLastError());
     }
-    (void)hipFree(lens); (void)hipFree(tmp);
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (e != hipSuccess) {
-        (void)hipFree(d);
-        return fail(h, BFTSIM_EHIP, std::string("trace size pass: ") + hipGetErrorString(e));
-    }
-    h->d_tfoff = d;
-    h->trace_ioff = std::move(ioff);
+    if (t1) HIPCHECK(h, hipEventRecord(t1, s));
+    HIPCHECK(h, hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, s));
+    HIPCHECK(h, hipStreamSynchronize(s));
+    if (err)
+        return fail(h, BFTSIM_EHIP, std::string(what) + ": " + std::to_string(err) +
+                                        " frames whose emitted length differs from the counted one");
     return BFTSIM_OK;
 }
 
@@ -2099,61 +2041,28 @@ int bftsim_export_trace(bftsim_t* h, uint64_t inst_begin, uint64_t inst_count, u
     if (stream_cap < bytes || (bytes && !stream))
         return fail(h, BFTSIM_EINVAL, "bftsim_export_trace: stream_cap " + std::to_string(stream_cap) + " < " +
                                           std::to_string(bytes) + " bytes");
-    // the serial emitter: the A/B arm of scripts/trace_bench.py only. A handle prepared without BFTSIM_TESTING=1
-    // (the product path) reads no environment here; a testing handle reads the switch per call, so that the arms
-    // interleave
-    const char* ser = h->testing ? getenv("BFTSIM_TRACE_SERIAL") : nullptr;
-    const bool serial = ser && atoi(ser) == 1;
     HIPCHECK(h, hipSetDevice(h->device));
     hipStream_t s = h->last_stream;
-    uint8_t* d_out = nullptr;
-    uint32_t* d_meta = nullptr;
-    uint32_t* d_err = (uint32_t*)(h->d_tfoff + h->trace_M + 1 + n + 1);
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    uint32_t err = 0;
-    hipError_t e = hipMalloc(&d_out, bytes + 16);
-    if (e == hipSuccess && frame_meta && frames) e = hipMalloc(&d_meta, frames * 16);
-    for (int k = 0; k < 4 && e == hipSuccess; ++k) e = hipEventCreate(&ev[k]);
-    if (e == hipSuccess) e = hipMemsetAsync(d_err, 0, 4, s);
-    if (e == hipSuccess) e = hipEventRecord(ev[0], s);
-    if (e == hipSuccess && frames) {
-        bft::Params p = make_params(h, h->last_first, n);
-        const dim3 g((uint32_t)((frames + 63) / 64));
-        if (serial)
-            hipLaunchKernelGGL(bft::bft_trace_emit_serial_kernel, g, dim3(64), 0, s, p, h->trace_args, m0, m1, h->d_tfoff,
-                               d_out, d_err);
-        else
-            hipLaunchKernelGGL(bft::bft_trace_emit_kernel, g, dim3(64), 0, s, p, h->trace_args, m0, m1, h->d_tfoff, d_out,
-                               d_err);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipEventRecord(ev[1], s);
-    if (e == hipSuccess && d_meta) {
+    DevMem d_out, d_meta;
+    Events ev;
+    HIPCHECK(h, d_out.alloc(bytes + 16));
+    if (frame_meta && frames) HIPCHECK(h, d_meta.alloc(frames * 16));
+    HIPCHECK(h, ev.create(4));
+    if (d_meta.p) {
         hipLaunchKernelGGL(bft::bft_trace_meta_kernel, dim3((uint32_t)((frames + 255) / 256)), dim3(256), 0, s,
-                           h->trace_args, m0, m1, (uint32_t)inst_begin, d_meta);
-        e = hipGetLastError();
+                           h->trace_args, m0, m1, (uint32_t)inst_begin, d_meta.as<uint32_t>());
+        HIPCHECK(h, hipGetLastError());
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (int rc = trace_emit(h, "bftsim_export_trace", m0, m1, d_out.as<uint8_t>(), ev[0], ev[1])) return rc;
     // the passes agreed on every frame: only now is anything written to the caller's buffers
-    if (e == hipSuccess && err == 0) {
-        e = hipEventRecord(ev[2], s);
-        if (e == hipSuccess && bytes) e = hipMemcpyAsync(stream, d_out, bytes, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(frame_off, h->d_tfoff + m0, (frames + 1) * 8, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess && d_meta) e = hipMemcpyAsync(frame_meta, d_meta, frames * 16, hipMemcpyDeviceToHost, s);
-        if (e == hipSuccess) e = hipEventRecord(ev[3], s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e == hipSuccess) e = hipEventElapsedTime(&h->trace_ms[1], ev[0], ev[1]);
-        if (e == hipSuccess) e = hipEventElapsedTime(&h->trace_ms[2], ev[2], ev[3]);
-    }
-    (void)hipFree(d_out); (void)hipFree(d_meta);
-    for (int k = 0; k < 4; ++k)
-        if (ev[k]) (void)hipEventDestroy(ev[k]);
-    if (e != hipSuccess) return fail(h, BFTSIM_EHIP, std::string("bftsim_export_trace: ") + hipGetErrorString(e));
-    if (err)
-        return fail(h, BFTSIM_EHIP, "bftsim_export_trace: " + std::to_string(err) +
-                                        " frames whose emitted length differs from the counted one");
+    HIPCHECK(h, hipEventRecord(ev[2], s));
+    if (bytes) HIPCHECK(h, hipMemcpyAsync(stream, d_out.p, bytes, hipMemcpyDeviceToHost, s));
+    HIPCHECK(h, hipMemcpyAsync(frame_off, h->d_tfoff + m0, (frames + 1) * 8, hipMemcpyDeviceToHost, s));
+    if (d_meta.p) HIPCHECK(h, hipMemcpyAsync(frame_meta, d_meta.p, frames * 16, hipMemcpyDeviceToHost, s));
+    HIPCHECK(h, hipEventRecord(ev[3], s));
+    HIPCHECK(h, hipStreamSynchronize(s));
+    HIPCHECK(h, hipEventElapsedTime(&h->trace_ms[1], ev[0], ev[1]));
+    HIPCHECK(h, hipEventElapsedTime(&h->trace_ms[2], ev[2], ev[3]));
     const uint64_t base = frame_off[0];
     for (uint64_t k = 0; k <= frames; ++k) frame_off[k] -= base;
     if (inst_frame0)
@@ -2197,73 +2106,61 @@ static int audit_device(bftsim* h, const uint8_t* d_stream, const uint64_t* d_fo
                    o_if0 = sized((inst + 1) * 8), o_keys = sized(Ix * key_cap * sizeof(A::Key)), o_iflags = sized(Ix * 4),
                    o_cround = sized(Rx * 2), o_cdig = sized(Rx * 32), o_cvot = sized(Rx * 32), o_cframe = sized(Rx * 4),
                    o_cflags = sized(Rx), o_counts = sized(A::CNT_WORDS * 8), o_nseal = sized(4);
-    uint8_t* pool = nullptr;
-    if (hipMalloc(&pool, bytes) != hipSuccess)
+    DevMem pool_mem;
+    if (pool_mem.alloc(bytes) != hipSuccess)
         return fail(h, BFTSIM_ENOMEM, "bftsim_audit: " + std::to_string(bytes) + " bytes of device memory");
+    uint8_t* pool = pool_mem.as<uint8_t>();
     A::Recs r{pool + o_st, pool + o_code, (uint32_t*)(pool + o_hx), (uint64_t*)(pool + o_round), pool + o_dig, pool + o_sdig,
               pool + o_sig, (uint32_t*)(pool + o_sk), (uint32_t*)(pool + o_want), pool + o_sldig, pool + o_seal};
     unsigned long long* d_counts = (unsigned long long*)(pool + o_counts);
     uint32_t* d_nseal = (uint32_t*)(pool + o_nseal);
     uint64_t* d_if0 = (uint64_t*)(pool + o_if0);
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    hipError_t e = hipSuccess;
-    int rc = BFTSIM_OK;
-    for (int k = 0; k < 5 && e == hipSuccess; ++k) e = hipEventCreate(&ev[k]);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_if0, if0, (inst + 1) * 8, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemsetAsync(d_counts, 0, A::CNT_WORDS * 8 + 4, s);            // the counters and n_seals
-    if (e == hipSuccess) e = hipMemsetAsync(pool + o_cround, 0xff, Rx * 2, s);                // ROUND_NONE
-    if (e == hipSuccess) e = hipMemsetAsync(pool + o_cdig, 0, o_counts - o_cdig, s);          // the other certificate rows
-    if (e == hipSuccess) e = hipMemsetAsync(pool + o_iflags, 0, Ix * 4, s);
+    Events ev;
+    HIPCHECK(h, ev.create(5));
+    HIPCHECK(h, hipMemcpyAsync(d_if0, if0, (inst + 1) * 8, hipMemcpyHostToDevice, s));
+    HIPCHECK(h, hipMemsetAsync(d_counts, 0, A::CNT_WORDS * 8 + 4, s));            // the counters and n_seals
+    HIPCHECK(h, hipMemsetAsync(pool + o_cround, 0xff, Rx * 2, s));                // ROUND_NONE
+    HIPCHECK(h, hipMemsetAsync(pool + o_cdig, 0, o_counts - o_cdig, s));          // the other certificate rows
+    HIPCHECK(h, hipMemsetAsync(pool + o_iflags, 0, Ix * 4, s));
     // decode
     uint32_t n_seals = 0;
-    if (e == hipSuccess) e = hipEventRecord(ev[0], s);
-    if (e == hipSuccess)
-        e = A::launch_decode(A::DecodeArgs{d_stream, d_foff, base, F, h->d_addr, h->cfg.n,
-                                           h->cfg.seed_byte_order == BFTSIM_SEED_LE ? 1u : 0u, max_heights, r, d_nseal}, s);
-    if (e == hipSuccess) e = hipEventRecord(ev[1], s);
-    if (e == hipSuccess) e = hipMemcpyAsync(&n_seals, d_nseal, 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    HIPCHECK(h, hipEventRecord(ev[0], s));
+    HIPCHECK(h, A::launch_decode(A::DecodeArgs{d_stream, d_foff, base, F, h->d_addr, h->cfg.n,
+                                               h->cfg.seed_byte_order == BFTSIM_SEED_LE ? 1u : 0u, max_heights, r, d_nseal}, s));
+    HIPCHECK(h, hipEventRecord(ev[1], s));
+    HIPCHECK(h, hipMemcpyAsync(&n_seals, d_nseal, 4, hipMemcpyDeviceToHost, s));
+    HIPCHECK(h, hipStreamSynchronize(s));
     // recoveries: every frame's signer, every decodable Commit's seal
-    if (e == hipSuccess && F && sa.recover(h->sig, r.sdig, r.sig, F, nullptr, pool + o_raddr, pool + o_rok, s) != 0)
-        rc = fail(h, BFTSIM_EHIP, std::string("bftsig_recover: ") + sa.last_error(h->sig));
-    if (e == hipSuccess && rc == 0 && n_seals &&
-        sa.recover(h->sig, r.seal_dig, r.seal, n_seals, nullptr, pool + o_saddr, pool + o_sok, s) != 0)
-        rc = fail(h, BFTSIM_EHIP, std::string("bftsig_recover (seals): ") + sa.last_error(h->sig));
-    if (e == hipSuccess && rc == 0) e = hipEventRecord(ev[2], s);
+    if (F && sa.recover(h->sig, r.sdig, r.sig, F, nullptr, pool + o_raddr, pool + o_rok, s) != 0)
+        return fail(h, BFTSIM_EHIP, std::string("bftsig_recover: ") + sa.last_error(h->sig));
+    if (n_seals && sa.recover(h->sig, r.seal_dig, r.seal, n_seals, nullptr, pool + o_saddr, pool + o_sok, s) != 0)
+        return fail(h, BFTSIM_EHIP, std::string("bftsig_recover (seals): ") + sa.last_error(h->sig));
+    HIPCHECK(h, hipEventRecord(ev[2], s));
     // classification and tally
     uint8_t* d_status = pool + o_status;
     int32_t* d_signer = (int32_t*)(pool + o_signer);
-    if (e == hipSuccess && rc == 0)
-        e = A::launch_classify(A::ClassifyArgs{r, F, h->d_addr, h->cfg.n, pool + o_raddr, pool + o_rok, pool + o_saddr,
-                                               pool + o_sok, d_status, d_signer, d_counts}, s);
-    if (e == hipSuccess && rc == 0)
-        e = A::launch_tally(A::TallyArgs{r, d_status, d_signer, d_if0, inst, (A::Key*)(pool + o_keys), key_cap, max_heights,
-                                         bftsim_two_thirds_majority(h->cfg.n), (uint32_t*)(pool + o_iflags),
-                                         (uint16_t*)(pool + o_cround), pool + o_cdig, (uint64_t*)(pool + o_cvot),
-                                         (uint32_t*)(pool + o_cframe), pool + o_cflags, d_counts}, s);
-    if (e == hipSuccess && rc == 0) e = hipEventRecord(ev[3], s);
+    HIPCHECK(h, A::launch_classify(A::ClassifyArgs{r, F, h->d_addr, h->cfg.n, pool + o_raddr, pool + o_rok, pool + o_saddr,
+                                                   pool + o_sok, d_status, d_signer, d_counts}, s));
+    HIPCHECK(h, A::launch_tally(A::TallyArgs{r, d_status, d_signer, d_if0, inst, (A::Key*)(pool + o_keys), key_cap, max_heights,
+                                             bftsim_two_thirds_majority(h->cfg.n), (uint32_t*)(pool + o_iflags),
+                                             (uint16_t*)(pool + o_cround), pool + o_cdig, (uint64_t*)(pool + o_cvot),
+                                             (uint32_t*)(pool + o_cframe), pool + o_cflags, d_counts}, s));
+    HIPCHECK(h, hipEventRecord(ev[3], s));
     unsigned long long c[A::CNT_WORDS] = {0};
-    if (e == hipSuccess && rc == 0) e = hipMemcpyAsync(c, d_counts, sizeof c, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && rc == 0) e = hipStreamSynchronize(s);      // every pass succeeded: only now the caller's buffers
-    if (e == hipSuccess && rc == 0 && out) {
-        auto back = [&](void* dst, uint64_t off, uint64_t b) {
-            if (dst && b && e == hipSuccess) e = hipMemcpyAsync(dst, pool + off, b, hipMemcpyDeviceToHost, s);
-        };
-        back(out->frame_status, o_status, F); back(out->frame_signer, o_signer, F * 4);
-        back(out->inst_flags, o_iflags, inst * 4);
-        back(out->cert_round, o_cround, rows * 2); back(out->cert_digest, o_cdig, rows * 32);
-        back(out->cert_voters, o_cvot, rows * 32); back(out->cert_frame, o_cframe, rows * 4);
-        back(out->cert_flags, o_cflags, rows);
+    HIPCHECK(h, hipMemcpyAsync(c, d_counts, sizeof c, hipMemcpyDeviceToHost, s));
+    HIPCHECK(h, hipStreamSynchronize(s));      // every pass succeeded: only now the caller's buffers
+    if (out) {
+        const struct { void* dst; uint64_t off, b; } back[] = {
+            {out->frame_status, o_status, F}, {out->frame_signer, o_signer, F * 4}, {out->inst_flags, o_iflags, inst * 4},
+            {out->cert_round, o_cround, rows * 2}, {out->cert_digest, o_cdig, rows * 32}, {out->cert_voters, o_cvot, rows * 32},
+            {out->cert_frame, o_cframe, rows * 4}, {out->cert_flags, o_cflags, rows}};
+        for (const auto& k : back)
+            if (k.dst && k.b) HIPCHECK(h, hipMemcpyAsync(k.dst, pool + k.off, k.b, hipMemcpyDeviceToHost, s));
     }
-    if (e == hipSuccess && rc == 0) e = hipEventRecord(ev[4], s);
-    if (e == hipSuccess && rc == 0) e = hipStreamSynchronize(s);
+    HIPCHECK(h, hipEventRecord(ev[4], s));
+    HIPCHECK(h, hipStreamSynchronize(s));
     float ms[4] = {0, 0, 0, 0};
-    for (int k = 0; k < 4 && e == hipSuccess && rc == 0; ++k) e = hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]);
-    (void)hipFree(pool);
-    for (int k = 0; k < 5; ++k)
-        if (ev[k]) (void)hipEventDestroy(ev[k]);
-    if (rc) return rc;
-    if (e != hipSuccess) return fail(h, BFTSIM_EHIP, std::string("bftsim_audit: ") + hipGetErrorString(e));
+    for (int k = 0; k < 4; ++k) HIPCHECK(h, hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]));
     h->audit_ms[0] = ms[0]; h->audit_ms[1] = ms[1]; h->audit_ms[2] = ms[2]; h->audit_ms[3] = ms[3] + copy_in_ms;
     memset(report, 0, sizeof *report);
     report->frames = F;
@@ -2302,29 +2199,22 @@ int bftsim_audit_trace(bftsim_t* h, const uint8_t* stream, uint64_t stream_bytes
     HIPCHECK(h, hipSetDevice(h->device));
     if (int rc = audit_sig(h)) return rc;
     hipStream_t s = h->last_stream;
-    uint8_t* d_in = nullptr;
+    DevMem in_mem;
     const uint64_t sb = (stream_bytes + 15) & ~15ull;              // the frame offsets follow the padded stream
-    if (hipMalloc(&d_in, sb + 16 + (frames + 1) * 8) != hipSuccess)
+    if (in_mem.alloc(sb + 16 + (frames + 1) * 8) != hipSuccess)
         return fail(h, BFTSIM_ENOMEM, "bftsim_audit_trace: device memory for the stream");
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    uint8_t* d_in = in_mem.as<uint8_t>();
+    Events ev;
     float copy_ms = 0;
-    hipError_t e = hipEventCreate(&e0);
-    if (e == hipSuccess) e = hipEventCreate(&e1);
-    if (e == hipSuccess) e = hipEventRecord(e0, s);
-    if (e == hipSuccess && stream_bytes) e = hipMemcpyAsync(d_in, stream, stream_bytes, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_in + sb + 16, frame_off, (frames + 1) * 8, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipEventRecord(e1, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e == hipSuccess) e = hipEventElapsedTime(&copy_ms, e0, e1);
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    int rc = BFTSIM_OK;
-    if (e != hipSuccess) rc = fail(h, BFTSIM_EHIP, std::string("bftsim_audit_trace: ") + hipGetErrorString(e));
-    if (rc == 0)
-        rc = audit_device(h, d_in, (const uint64_t*)(d_in + sb + 16), 0, frames, inst_frame0, inst_count, max_heights, key_cap,
-                          out, report, s, copy_ms);
-    (void)hipFree(d_in);
-    return rc;
+    HIPCHECK(h, ev.create(2));
+    HIPCHECK(h, hipEventRecord(ev[0], s));
+    if (stream_bytes) HIPCHECK(h, hipMemcpyAsync(d_in, stream, stream_bytes, hipMemcpyHostToDevice, s));
+    HIPCHECK(h, hipMemcpyAsync(d_in + sb + 16, frame_off, (frames + 1) * 8, hipMemcpyHostToDevice, s));
+    HIPCHECK(h, hipEventRecord(ev[1], s));
+    HIPCHECK(h, hipStreamSynchronize(s));
+    HIPCHECK(h, hipEventElapsedTime(&copy_ms, ev[0], ev[1]));
+    return audit_device(h, d_in, (const uint64_t*)(d_in + sb + 16), 0, frames, inst_frame0, inst_count, max_heights, key_cap,
+                        out, report, s, copy_ms);
 }
 
 int bftsim_audit_last_trace(bftsim_t* h, uint64_t inst_begin, uint64_t inst_count, uint32_t key_cap,
@@ -2345,29 +2235,12 @@ int bftsim_audit_last_trace(bftsim_t* h, uint64_t inst_begin, uint64_t inst_coun
     std::vector<uint64_t> if0(inst_count + 1);
     for (uint64_t i = 0; i <= inst_count; ++i) if0[i] = h->trace_moff[inst_begin + i] - m0;
     // the emit pass of bftsim_export_trace into a device stream that stays on the device
-    uint8_t* d_out = nullptr;
-    uint32_t* d_err = (uint32_t*)(h->d_tfoff + h->trace_M + 1 + n + 1);
-    uint32_t err = 0;
-    if (hipMalloc(&d_out, ((bytes + 15) & ~15ull) + 16) != hipSuccess)
+    DevMem d_out;
+    if (d_out.alloc(((bytes + 15) & ~15ull) + 16) != hipSuccess)
         return fail(h, BFTSIM_ENOMEM, "bftsim_audit_last_trace: device memory for the stream");
-    hipError_t e = hipMemsetAsync(d_err, 0, 4, s);
-    if (e == hipSuccess && frames) {
-        bft::Params p = make_params(h, h->last_first, n);
-        hipLaunchKernelGGL(bft::bft_trace_emit_kernel, dim3((uint32_t)((frames + 63) / 64)), dim3(64), 0, s, p, h->trace_args,
-                           m0, m1, h->d_tfoff, d_out, d_err);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    int rc = BFTSIM_OK;
-    if (e != hipSuccess) rc = fail(h, BFTSIM_EHIP, std::string("bftsim_audit_last_trace: ") + hipGetErrorString(e));
-    else if (err) rc = fail(h, BFTSIM_EHIP, "bftsim_audit_last_trace: " + std::to_string(err) +
-                                               " frames whose emitted length differs from the counted one");
-    if (rc == 0)
-        rc = audit_device(h, d_out, h->d_tfoff + m0, base, frames, if0.data(), inst_count, h->cfg.heights, key_cap, out,
-                          report, s, 0.f);
-    (void)hipFree(d_out);
-    return rc;
+    if (int rc = trace_emit(h, "bftsim_audit_last_trace", m0, m1, d_out.as<uint8_t>(), nullptr, nullptr)) return rc;
+    return audit_device(h, d_out.as<uint8_t>(), h->d_tfoff + m0, base, frames, if0.data(), inst_count, h->cfg.heights,
+                        key_cap, out, report, s, 0.f);
 }
 
 int bftsim_audit_last_ms(bftsim_t* h, float* decode_ms, float* recover_ms, float* tally_ms, float* copy_ms) {

@@ -28,12 +28,8 @@ void bft_consensus_fast_kernel(Params p) {
 #define BFT_CONSENSUS_PRIO 2
 #endif
     // win issue arbitration against the hash waves of the previous launch (the hash pass stretches into
-    // the issue gaps and still finishes within the step); s_setprio takes an immediate
-    if (p.fast_prio == 0u) __builtin_amdgcn_s_setprio(BFT_CONSENSUS_PRIO);
-    else if (p.fast_prio == 1u) __builtin_amdgcn_s_setprio(0);
-    else if (p.fast_prio == 2u) __builtin_amdgcn_s_setprio(1);
-    else if (p.fast_prio == 3u) __builtin_amdgcn_s_setprio(2);
-    else __builtin_amdgcn_s_setprio(3);
+    // the issue gaps and still finishes within the step)
+    __builtin_amdgcn_s_setprio(BFT_CONSENSUS_PRIO);
     Fast64<WaveHip, LOSSY, SEEDED> sim(p, lds, blockIdx.x);
     sim.run();
 }
@@ -41,7 +37,7 @@ hipError_t launch_fast(dim3 grid, hipStream_t s, const Params& p) {
     // the lossless build for schedules without drops and proposer crashes (cfg3): masks are constants;
     // SEEDED (little-endian seeds): the proposer follows the block hashes, computed in-kernel
     const bool lossy = !(p.thr16 == 0 && p.crash_on == 0), seeded = p.need_seed != 0;
-    const size_t lds = lds_bytes_fast64(seeded) + p.fast_lds_pad;   // the pad: A/B arms of FAST residency only
+    const size_t lds = lds_bytes_fast64(seeded);
     if (seeded) {
         if (lossy) hipLaunchKernelGGL((bft_consensus_fast_kernel<true, true>), grid, dim3(64), lds, s, p);
         else hipLaunchKernelGGL((bft_consensus_fast_kernel<false, true>), grid, dim3(64), lds, s, p);
@@ -350,7 +346,7 @@ __device__ inline void keccak_f1600_lane(uint32_t L[25], uint32_t H[25]) {
 // so that more consensus waves fit a CU beside two chain waves per SIMD.
 constexpr uint32_t SFX_LDS_DW = 56;
 static_assert(SFX_LDS_DW * 4u >= 213u && SFX_LDS_DW <= SFX_BODY_DW && SFX_LDS_DW % 2u == 0u, "inline suffix column");
-// Large shards (>= 8,192 instances per launch, bftsim.hip chain_lane_min): a LANE per instance. The whole state in
+// Large shards (>= 6,144 instances per launch, bftsim.hip chain_lane_min): a LANE per instance. The whole state in
 // one lane: ~180 VALU per round instead of 2 x 118 for a lane pair, i.e. ~24 % fewer instructions per header for
 // ~1.5x the chain latency, which a large shard's throughput-bound pipeline hides (cfg3 at 16,384: 1.70e9 with lane
 // pairs, 1.82e9-1.85e9 with lanes in batches of 12; profiles/r06/ab_lane).

@@ -1,9 +1,8 @@
 #!/usr/bin/env python3
 """Measures the trace export (bftsim_export_trace, SPEC.md §11b) on one GPU at the crypto line's
 shape: cfg3, 1,024 instances x 10 heights, every broadcast signed. After one launch + bftsim_crypto_verify (keep on)
-it exports the whole launch 1 + 5 times per arm, the two emit kernels interleaved:
-  coop    a wave per 64 frames through an LDS stage, 16-byte coalesced stores (the library's emitter)
-  serial  a lane per frame, byte stores to global memory (BFTSIM_TRACE_SERIAL=1 on a BFTSIM_TESTING=1 handle)
+it exports the whole launch 1 + 5 times with the library's emitter (`coop`: a wave per 64 frames through an LDS
+stage, 16-byte coalesced stores; the lane-per-frame emitter it was measured against is retired)
 and records, from the library's HIP events, the emit kernel's frames/s and device-side GB/s, the device-to-host
 copy time, the size pass, and the wall time of the verify pass in the same process.
 
@@ -36,7 +35,6 @@ def main():
     import secp256k1_ref as S                              # the addresses on the CPU: libbftsim is all this needs
     sec = synthetic_secrets(64, 3)
     cfg, secrets = keyed_config(cfg3(heights=args.heights), sec, [S.address(S.pubkey(k), keccak256) for k in sec])
-    os.environ["BFTSIM_TESTING"] = "1"                     # a testing handle: the library reads the emitter switch
     sim = Simulator(cfg)
     sim.set_crypto(secrets, (), 24_576)
     sim.set_trace_keep(True)
@@ -55,26 +53,19 @@ def main():
     size_ms = sim.trace_ms()[0]
     frames, nbytes = int(fr.sum()), int(by.sum())
     stream, off = np.zeros(nbytes, np.uint8), np.zeros(frames + 1, np.uint64)
-    arms = {"coop": [], "serial": []}
-    first = {}
+    rows = []
     for r in range(1 + args.repeats):
-        for arm in ("coop", "serial"):
-            if arm == "serial":
-                os.environ["BFTSIM_TRACE_SERIAL"] = "1"
-            t0 = time.perf_counter()
-            rc = lib().bftsim_export_trace(sim.h, 0, args.instances, stream.ctypes.data, nbytes, off.ctypes.data, frames,
-                                           None, None)
-            wall = time.perf_counter() - t0
-            os.environ.pop("BFTSIM_TRACE_SERIAL", None)
-            _check(sim.h, rc, "bftsim_export_trace")
-            _, emit_ms, copy_ms = sim.trace_ms()
-            if r == 0:                                       # warm-up; and the arms must agree byte for byte
-                dig = ctypes.create_string_buffer(32)
-                lib().bftsim_keccak256(ctypes.cast(stream.ctypes.data, ctypes.c_char_p), nbytes, dig)
-                first[arm] = dig.raw
-                continue
-            arms[arm].append(dict(emit_ms=emit_ms, copy_ms=copy_ms, wall_ms=1000 * wall))
-    assert first["coop"] == first["serial"], "the two emitters disagree"
+        t0 = time.perf_counter()
+        rc = lib().bftsim_export_trace(sim.h, 0, args.instances, stream.ctypes.data, nbytes, off.ctypes.data, frames,
+                                       None, None)
+        wall = time.perf_counter() - t0
+        _check(sim.h, rc, "bftsim_export_trace")
+        _, emit_ms, copy_ms = sim.trace_ms()
+        if r == 0:                                           # warm-up; the stream's digest identifies the bytes
+            dig = ctypes.create_string_buffer(32)
+            lib().bftsim_keccak256(ctypes.cast(stream.ctypes.data, ctypes.c_char_p), nbytes, dig)
+            continue
+        rows.append(dict(emit_ms=emit_ms, copy_ms=copy_ms, wall_ms=1000 * wall))
     sim.close()
 
     def summary(rows):
@@ -84,11 +75,11 @@ def main():
                     frames_per_s=frames / (med * 1e-3), device_GB_per_s=nbytes / (med * 1e-3) / 1e9,
                     copy_ms=[round(x["copy_ms"], 3) for x in rows], wall_ms=[round(x["wall_ms"], 3) for x in rows])
 
-    out = dict(shape=f"cfg3, {args.instances} instances x {args.heights} heights, one GPU; 1 warm-up + {args.repeats} repeats, arms interleaved",
+    out = dict(shape=f"cfg3, {args.instances} instances x {args.heights} heights, one GPU; 1 warm-up + {args.repeats} repeats",
                frames=frames, stream_bytes=nbytes, mean_frame_bytes=nbytes / max(frames, 1),
                messages=rep["messages"], seals=rep["seals"],
                verify_wall_ms=[round(1000 * x, 2) for x in verify_s[1:]], size_pass_ms=size_ms, sizes_call_wall_ms=1000 * sizes_wall,
-               coop=summary(arms["coop"]), serial=summary(arms["serial"]), stream_keccak256=first["coop"].hex())
+               coop=summary(rows), stream_keccak256=dig.raw.hex())
     vmed = sorted(verify_s[1:])[len(verify_s[1:]) // 2]
     out["emit_over_verify"] = out["coop"]["emit_ms_median"] * 1e-3 / vmed
     out["export_wall_over_verify"] = sorted(out["coop"]["wall_ms"])[len(out["coop"]["wall_ms"]) // 2] * 1e-3 / vmed

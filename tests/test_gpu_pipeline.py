@@ -340,3 +340,30 @@ def test_little_endian_pipelined_predictions(name, mk, depth, monkeypatch):
     ref = O.run(cfg, 5 * n, n)
     assert_same(ref, outs[0], name + " predictions")
     assert_same(ref, outs[1], name + " wave hash only")
+
+
+def test_pmc_evict_attribution_pass(monkeypatch):
+    """BFTSIM_PMC_EVICT=1 (the attribution pass of scripts/gpu_profile.sh): a 64 MiB read after every kernel of a
+    launch, on the launch's own stream, changes no result -- unpipelined, and at pipeline depth 2 with three
+    launches over distinct instance ranges (the eviction also follows the suffix, chain and check kernels on the
+    hash streams); the last launch against the oracle. This covers the knob's code path for parity only: the
+    eviction has no result of its own, so the test would also pass if the knob were ignored (whether it evicts
+    is what scripts/gpu_profile.sh's WRITE_SIZE attribution shows)."""
+    monkeypatch.setenv("BFTSIM_TESTING", "1")
+    monkeypatch.setenv("BFTSIM_PMC_EVICT", "1")
+    cfg = cfg3(heights=10)
+    n = 64
+    ref = O.run(cfg, 2 * n, n)
+    for depth in (0, 2):
+        sim = _sim(cfg)
+        try:
+            if depth:
+                sim.set_pipeline(True, depth)
+            sim.prepare(n)
+            for k in range(3) if depth else (2,):
+                sim.launch(k * n)
+            sim.sync()
+            got = sim.fetch()
+        finally:
+            sim.close()
+        assert_same(ref, got, f"pmc evict, pipeline depth {depth}")
