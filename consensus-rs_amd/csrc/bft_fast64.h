@@ -31,7 +31,18 @@
 #include "bft_kwave.h"
 #include "bft_wave.h"
 
+// CPU emulator build (tests/emu, -DBFT_EMU_CHECKS), host compiler only: canonical_run()'s counters and off switch
+#if defined(BFT_EMU_CHECKS) && !defined(__HIP_DEVICE_COMPILE__) && !defined(__HIPCC__)
+#define BFT_EMU_CANON 1
+#include <stdlib.h>
+#endif
+
 namespace bft {
+
+#ifdef BFT_EMU_CANON
+// {heights recorded by Fast64::canonical_run, heights recorded tick by tick (record_canon)} since the last reset
+inline uint64_t* emu_canon_counts() { static uint64_t c[2] = {0, 0}; return c; }
+#endif
 
 // LDS per wave (bytes)
 struct F64Layout {
@@ -275,6 +286,7 @@ struct Fast64 {
             // scalar loop over the active lanes)
             uint32_t* lb = (uint32_t*)(lds + F64Layout::LAT_OFF) + (lat < 64u ? lat : 64u);
             *lb += cnt;
+            canon_tick_count(1u);
             uint32_t* r = ring_row(x);
             r[0] = 0; r[1] = blk_prop(b) | (blk_var(b) << 16) | (1u << 24); r[2] = blk_T(b); r[3] = 0;   // seed: hash_pending
         }
@@ -785,6 +797,112 @@ struct Fast64 {
         return true;
     }
 
+    // ------------------------------------------------------------------ a run of canonical ticks, composed
+    // Big-endian seeds (proposer j = 0 at every height), lossless schedule. Entry: canonical_tick() has just
+    // returned true at tick t for height H and the block time was the tick itself (ptout == t). Its last
+    // lines then left every lane with wake_tick = t + 1, last = canon_h = H, mint_height = H + 1,
+    // miner_queue = nxf = 0, the Prepare / Commit cache heights = H and cand_T = t + 1, and touched neither
+    // L_DEAD nor L_SYNCP: that is canonical_tick()'s whole ballot for height H + 1 at tick t + 1 (its `bad`
+    // word is 0 on every lane; pp_hit is 0 because the proposer's Preprepare cache holds height H), and the
+    // block time of H + 1 is again its tick. By induction every following tick is canonical until one of
+    //   canon_h < P.heights, tick + 1 < P.max_ticks, H + 1 < P.hcap, k0 != k1 at H + 1
+    // fails (frozen, phase_cap >= 5, macro_ok and the Byzantine set do not change on the way).
+    // Each of those ticks rewrites, on every lane and without reading them, h, pp, prep, comm, the state and
+    // lock bits of fl, the timers, last, last_T, cand_T, the miner fields, the outbox words, W_PENDT and the
+    // three outbound-cache entries: between two canonical ticks nothing reads them, so only the last tick's
+    // values are live. What a height leaves behind for good is its record row, one view, one count in latency
+    // bucket 1 (tick - canon_tick = 1) and, at the end, canon_h / canon_tip / canon_tick / tick.
+    // So: one lane per height. Lane l takes height canon_h + 1 + l at tick t + 1 + l, draws that height's
+    // SPLIT word itself when the proposer equivocates (split_mask draws one height on all 64 lanes), decides
+    // k0 / k1 as canonical_tick() does, and the leading lanes that pass store their rows straight to P.rec,
+    // 16 B each. Nothing is stored above the new canon_h. The per-lane state is then set once, for the last
+    // height of the run. A height with k0 == k1 stops the run in front of it: the caller's loop calls
+    // canonical_tick() at exactly that tick, which declines, and the T-step and phase loop take it as before.
+    // Bit-identical by construction; tests/test_emu_canon_run.py, tests/test_gpu_canon_run.py, the fuzzer.
+    BFT_FN void canonical_run() {
+        if (!canon_run_enabled()) return;
+        const uint32_t j = 0u;
+        const bool eq = ((byz_mask >> j) & 1ull) != 0;              // the proposer is Byzantine (uniform)
+        const uint64_t hon = ~byz_mask;
+        uint64_t v1m_e = 0;                                         // the last height's split and variant
+        bool k1_e = false;
+        uint32_t total = 0;
+        flush_rows();                                               // the ring is empty from here on
+        for (;;) {
+            const uint32_t Hn = canon_h + 1u + me;
+            const uint32_t tk = (uint32_t)tick + 1u + me;
+            uint64_t v1m = 0;
+            if (eq) {
+                uint32_t w[4];
+                philox(seed(), inst, Hn, 0, DOM_SPLIT, w);
+                v1m = ((uint64_t)w[0] | ((uint64_t)w[1] << 32)) & ~(1ull << j);
+            }
+            const bool k0 = popc(byz_mask | (hon & ~v1m)) > Q, k1 = popc(byz_mask | (hon & v1m)) > Q;
+            const bool ok = (Hn <= P.heights) & (tk < P.max_ticks) & (Hn < P.hcap) & (k0 != k1);
+            const uint32_t R = ctz64(~ballot(ok));                  // leading lanes that pass
+            if (R == 0u) break;
+            if (me < R) wv.gstore4(rec_row(Hn), 0u, j | (k1 ? (1u << 16) : 0u) | (1u << 24), tk, 0u);
+            v1m_e = rl64(v1m, R - 1u);
+            k1_e = rl(k1 ? 1u : 0u, R - 1u) != 0u;
+            canon_h += R;
+            tick += (int32_t)R;
+            total += R;
+            flushed = canon_h;
+            if (R < 64u) break;
+        }
+        if (total == 0u) return;
+        const uint32_t H = canon_h, t = (uint32_t)tick;             // the last height and its tick = block time
+        views_acc += total;                                         // every height here is <= P.heights
+        if (me == 0) {
+            ((uint32_t*)(lds + F64Layout::LAT_OFF))[1] += total;
+            canon_run_count(total);
+        }
+        canon_tip = blk_make(H, j, k1_e ? 1u : 0u, t);
+        canon_tick = t;
+        // canonical_tick()'s per-lane result for (H, t)
+        uint32_t* pc = cache_p(0);
+        uint32_t* c1 = cache_p(2);
+        uint32_t* c2 = cache_p(4);
+        const uint32_t hd = (H & 0x3fffffu) | (j << 22) | 0x80000000u;
+        *lane_p(F64Layout::W_PENDT) = t;
+        if (me == j) { pc[0] = H; pc[64] = hd; }
+        pp_T_out = t;
+        const uint32_t vw = me < 32u ? (uint32_t)v1m_e : (uint32_t)(v1m_e >> 32);
+        const bool var = ((vw >> (me & 31u)) & 1u) != 0u;
+        const bool fires = var == k1_e;
+        const uint32_t d32 = hd | (var ? (1u << 30) : 0u);
+        c1[0] = H; c1[64] = d32;
+        c2[0] = H; c2[64] = d32;
+        h = H;
+        pp = blk_make(H, j, var ? 1u : 0u, t);
+        prep = ~0ull;
+        comm = byz_mask | (hon & (var ? v1m_e : ~v1m_e));
+        fl = (fl & ~(L_ST | L_WAIT | L_LOCK | L_PENDV | L_CMT)) | L_PROP | L_PENDV | L_LOCK |
+             (fires ? ST_COMMITTED : ST_PREPARED);
+        timer_tick = (int32_t)t + 1;
+        last = H;
+        last_T = (int32_t)t;
+        cand_T = t + 1u;
+        mint_height = H + 1u;
+        wake_tick = (int32_t)t + 1;
+        miner_queue = 0;
+        nxf = 0;
+        nx_blo = H;
+        nx_bhi = H;
+        wv.sync();
+    }
+    // CPU emulator build only: heights recorded by canonical_run() and tick by tick, and the run's off switch
+    // (BFT_EMU_CANON_RUN=0), for tests/test_emu_canon_run.py
+#ifdef BFT_EMU_CANON
+    static bool canon_run_enabled() { const char* e = getenv("BFT_EMU_CANON_RUN"); return !(e && e[0] == '0' && e[1] == 0); }
+    static void canon_run_count(uint32_t n) { emu_canon_counts()[0] += n; }
+    static void canon_tick_count(uint32_t n) { emu_canon_counts()[1] += n; }
+#else
+    BFT_FN static bool canon_run_enabled() { return true; }
+    BFT_FN static void canon_run_count(uint32_t) {}
+    BFT_FN static void canon_tick_count(uint32_t) {}
+#endif
+
     // ------------------------------------------------------------------ hand-over to the full kernel
     // the full kernel's save layout (bft_wave.h BFT_STATE_32 / BFT_STATE_64, then prep, comm, the 12
     // cache words, the bool bits, tick, phase); every implied field is expanded here
@@ -818,17 +936,37 @@ struct Fast64 {
         s[k++] = p;
     }
 
-    BFT_FN void init_byzantine() {       // partial Fisher-Yates by lane 0 (SPEC.md §5), LDS scratch
+    // partial Fisher-Yates (SPEC.md §5), LDS scratch. Draw i does not depend on the permutation, only the
+    // swaps are serial: lane i computes draw i and its swap index (one Philox and one division for the wave,
+    // instead of byz_count of each one after another on lane 0), then lane 0 does the swaps from those words.
+    // The lossless big-endian build only (there the serial draws were a fifth of the kernel); the lossy and
+    // little-endian builds keep lane 0's serial draws. The same mask as byz_mask64 either way.
+    BFT_FN void init_byzantine() {
+        constexpr bool PAR = !LOSSY && !SEEDED;
         uint8_t* perm = lds + F64Layout::RING_OFF;
         uint32_t* mw = (uint32_t*)(lds + F64Layout::RING_OFF + 64);
+        uint32_t* sw = (uint32_t*)(lds + F64Layout::RING_OFF + 128);   // PAR: 64 swap indices
+        if (PAR) {
+            uint32_t w[4];
+            philox(P.seed, inst, me, 0, DOM_BYZ, w);
+            sw[me] = me + w[0] % (N - me);
+            perm[me] = (uint8_t)me;
+            wv.sync();
+        }
         if (me == 0 && !seg_done) {
-            for (uint32_t i = 0; i < N; ++i) perm[i] = (uint8_t)i;
+            if (!PAR)
+                for (uint32_t i = 0; i < N; ++i) perm[i] = (uint8_t)i;
             uint64_t mask = 0;
             const uint32_t f = P.byz_count < N ? P.byz_count : N;
             for (uint32_t i = 0; i < f; ++i) {
-                uint32_t w[4];
-                philox(P.seed, inst, i, 0, DOM_BYZ, w);
-                const uint32_t j = i + w[0] % (N - i);
+                uint32_t j;
+                if (PAR) {
+                    j = sw[i];
+                } else {
+                    uint32_t w[4];
+                    philox(P.seed, inst, i, 0, DOM_BYZ, w);
+                    j = i + w[0] % (N - i);
+                }
                 const uint8_t t = perm[i]; perm[i] = perm[j]; perm[j] = t;
                 mask |= 1ull << perm[i];
             }
@@ -861,6 +999,8 @@ struct Fast64 {
             if (!LOSSY && macro_ok && tick != 0) {
                 bool stop = false;
                 while (canonical_tick()) {
+                    // big-endian seeds, block time = the tick: the canonical ticks that follow, at once
+                    if (!SEEDED && pp_T_out == (uint32_t)tick) canonical_run();
                     F64_STAMP(1);
                     if (canon_h >= P.heights) { seg_done = true; done_tick = (uint32_t)tick + 1; stop = true; break; }
                     if (++tick >= (int32_t)P.max_ticks) { stop = true; break; }
@@ -1026,3 +1166,12 @@ struct Fast64 {
 };
 
 }  // namespace bft
+
+#ifdef BFT_EMU_CANON
+// out[0..1] = emu_canon_counts(); reset != 0 clears them afterwards
+extern "C" __attribute__((used, visibility("default"))) inline void bft_emu_canon_counts(uint64_t* out, int reset) {
+    uint64_t* c = bft::emu_canon_counts();
+    out[0] = c[0]; out[1] = c[1];
+    if (reset) c[0] = c[1] = 0;
+}
+#endif
