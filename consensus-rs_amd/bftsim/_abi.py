@@ -53,6 +53,27 @@ class CAuditOut(ctypes.Structure):
         "cert_flags")]
 
 
+class CLedgerReport(ctypes.Structure):
+    _fields_ = [("headers", ctypes.c_uint64), ("by_status", ctypes.c_uint64 * 10)] + [(k, ctypes.c_uint64) for k in (
+        "votes", "recoveries", "duplicate_votes", "verified_instances")]
+
+
+class CLedgerOut(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in ("status", "block_hash", "voters", "n_votes", "verified_height")]
+
+
+def alloc_ledger(n_inst: int, heights: int):
+    """host buffers of bftsim_ledger_out -> (struct, arrays)"""
+    rows = n_inst * heights
+    arrs = dict(status=np.zeros(rows, np.uint8), block_hash=np.zeros(rows * 32, np.uint8),
+                voters=np.zeros(rows * 4, np.uint64), n_votes=np.zeros(rows, np.uint16),
+                verified_height=np.zeros(n_inst, np.uint64))
+    o = CLedgerOut()
+    for k, a in arrs.items():
+        setattr(o, k, a.ctypes.data)
+    return o, arrs
+
+
 def alloc_audit(frames: int, n_inst: int, heights: int):
     """host buffers of bftsim_audit_out (certificate rows preset to "none") -> (struct, arrays)"""
     rows = n_inst * heights

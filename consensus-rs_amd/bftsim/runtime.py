@@ -75,6 +75,11 @@ def lib():
         L.bftsim_audit_last_trace.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32,
                                               ctypes.POINTER(_abi.CAuditOut), ctypes.POINTER(_abi.CAuditReport)]
         L.bftsim_audit_last_ms.argtypes = [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_float)] * 4
+        L.bftsim_set_ledger_votes.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
+        L.bftsim_verify_ledger.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
+                                           ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(_abi.CLedgerOut),
+                                           ctypes.POINTER(_abi.CLedgerReport)]
+        L.bftsim_ledger_last_ms.argtypes = [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_float)] * 4
         L.bftsim_launched_count.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64),
                                             ctypes.POINTER(ctypes.c_uint64)]
         L.bftsim_comm_init.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_char_p]
@@ -392,6 +397,40 @@ class Simulator:
         """(decode, recoveries, classify + tally, copies) of the last audit, device ms (bftsim_audit_last_ms)."""
         v = [ctypes.c_float() for _ in range(4)]
         _check(self.h, lib().bftsim_audit_last_ms(self.h, *[ctypes.byref(x) for x in v]), "bftsim_audit_last_ms")
+        return tuple(x.value for x in v)
+
+    def set_ledger_votes(self, kind: str):
+        """What the next crypto_verify keeps as the ledger's votes: "signatures" (the Commit messages' signatures, the
+        default and the reference's) or "seals" (the Commits' seals, which verify_ledger can check;
+        bftsim_set_ledger_votes, SPEC.md §11d)."""
+        from .ledger import VOTE_KINDS
+        if kind not in VOTE_KINDS:
+            raise BftsimError(f"set_ledger_votes: {kind!r} is neither 'signatures' nor 'seals'")
+        _check(self.h, lib().bftsim_set_ledger_votes(self.h, VOTE_KINDS[kind]), "bftsim_set_ledger_votes")
+
+    def verify_ledger(self, ledger):
+        """The importer (include/bftsim.h bftsim_verify_ledger, SPEC.md §11d) over what export_ledger() returns (per
+        instance a list of header byte strings), or over raw (hdr, hdr_len, slot_bytes, heights) arrays in
+        bftsim_export_ledger's layout: every header verified from its bytes on the device. -> bftsim.ledger.Verdict"""
+        from .ledger import Verdict, pack
+        if isinstance(ledger, tuple):
+            hdr, lens, slot, H = ledger
+        else:
+            hdr, lens, slot, H = pack(ledger, heights=self.cfg.heights)
+        hdr = np.ascontiguousarray(hdr, np.uint8).reshape(-1)
+        lens = np.ascontiguousarray(lens, np.uint32).reshape(-1)
+        ok = 0 < H <= 65535                        # the library refuses it; no buffers are sized by it here
+        n = len(lens) // H if ok else 0
+        o, arrs = _abi.alloc_ledger(n, H if ok else 0)
+        rep = _abi.CLedgerReport()
+        _check(self.h, lib().bftsim_verify_ledger(self.h, hdr.ctypes.data, slot, lens.ctypes.data, n, H, ctypes.byref(o),
+                                                  ctypes.byref(rep)), "bftsim_verify_ledger")
+        return Verdict(arrs, rep, n, H)
+
+    def ledger_ms(self):
+        """(decode, recoveries, tally + link, copies) of the last verify_ledger, device ms (bftsim_ledger_last_ms)."""
+        v = [ctypes.c_float() for _ in range(4)]
+        _check(self.h, lib().bftsim_ledger_last_ms(self.h, *[ctypes.byref(x) for x in v]), "bftsim_ledger_last_ms")
         return tuple(x.value for x in v)
 
     @staticmethod

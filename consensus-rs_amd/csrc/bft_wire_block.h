@@ -67,8 +67,10 @@ BFT_FN void emit_tx(const E& e, const bftwire_tx& t) {
     emit_bytes(e, t.payload, t.payload_len);
     if (t.has_sig) emit_bytes(e, t.sig, 65); else e(0xc0);
 }
-template <class E>
-BFT_FN void emit_header(const E& e, const bftwire_block& b) {
+// the 12 fields of a Header in front of `votes`; B: a bftwire_block, or any record with its header fields (the
+// ledger's, bft_ledger.h, which keeps its votes where they lie)
+template <class E, class B>
+BFT_FN void emit_header_front(const E& e, const B& b) {
     mp_arr(e, 13);
     emit_bytes(e, b.prev_hash, 32);
     emit_address(e, b.proposer);
@@ -78,6 +80,10 @@ BFT_FN void emit_header(const E& e, const bftwire_block& b) {
     mp_uint(e, b.bloom); mp_uint(e, b.difficulty); mp_uint(e, b.height);
     mp_uint(e, b.gas_limit); mp_uint(e, b.gas_used); mp_uint(e, b.time);
     if (b.extra_len == BFTWIRE_NONE) e(0xc0); else emit_bytes(e, b.extra, b.extra_len);
+}
+template <class E>
+BFT_FN void emit_header(const E& e, const bftwire_block& b) {
+    emit_header_front(e, b);
     if (b.n_votes == BFTWIRE_NONE) { e(0xc0); return; }
     mp_arr(e, b.n_votes);                                   // Votes(Vec<Signature>): newtype, transparent
     for (uint32_t v = 0; v < b.n_votes; ++v) emit_bytes(e, b.votes[v], 65);

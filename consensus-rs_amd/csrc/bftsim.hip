@@ -30,6 +30,7 @@
 #include "bft_crypto.h"
 #include "bft_trace.h"
 #include "bft_audit.h"
+#include "bft_ledger.h"
 
 namespace bft {
 
@@ -270,9 +271,10 @@ __global__ __launch_bounds__(64) void bft_crypto_check_kernel(Params p, CryptoAr
 
 // pass 4 (lane per message): the signatures of the canonical committer's commit set (the block's votes,
 // core.rs:402-413 → backend.rs:163-174): each Commit of height x, the committed round, the committed
-// block (or a wildcard), from a sender in that set
+// block (or a wildcard), from a sender in that set. seals (bftsim_set_ledger_votes, SPEC.md §11d): the Commit's seal
+// a.seals[msg_k[m]] instead, which depends on the block alone and is what verify_seal recovers (backend.rs:343-367)
 __global__ __launch_bounds__(64) void bft_crypto_votes_kernel(Params p, CryptoArgs a, uint64_t M, uint8_t* vsig,
-                                                              uint8_t* vhas) {
+                                                              uint8_t* vhas, uint32_t seals) {
     const uint64_t m = (uint64_t)blockIdx.x * 64u + threadIdx.x;
     if (m >= M) return;
     const uint64_t ref = a.mref[m];
@@ -287,7 +289,8 @@ __global__ __launch_bounds__(64) void bft_crypto_votes_kernel(Params p, CryptoAr
     const uint32_t* vo = p.votes + ((uint64_t)il * p.rows + x) * 8;
     if (!((vo[sender >> 5] >> (sender & 31u)) & 1u)) return;
     const uint64_t slot = ((uint64_t)il * p.heights + (x - 1)) * p.n + sender;
-    for (int i = 0; i < 65; ++i) vsig[slot * 65 + i] = a.sigs[m * 65 + i];
+    const uint8_t* src = seals ? a.seals + (uint64_t)a.msg_k[m] * 65 : a.sigs + m * 65;
+    for (int i = 0; i < 65; ++i) vsig[slot * 65 + i] = src[i];
     vhas[slot] = 1;
 }
 
@@ -517,9 +520,10 @@ struct bftsim {
     uint8_t* d_keys = nullptr;        // [2N][32]: the validators' secrets, then their forged keys
     uint32_t* d_vsnap = nullptr;      // [cap_inst][seg][8] commit set at each lane's last commit
     uint32_t* d_votes = nullptr;      // [cap_inst][rows][8] canonical committer's commit set per height
-    uint8_t* d_vsig = nullptr;        // [last_n][H][N][65] the votes' signatures (bftsim_crypto_verify)
+    uint8_t* d_vsig = nullptr;        // [last_n][H][N][65] the votes' signatures, or their seals (bftsim_crypto_verify)
     uint8_t* d_vhas = nullptr;        // [last_n][H][N]
     uint64_t vsig_n = 0;              // instances d_vsig holds (0: no verify since the last launch)
+    uint32_t ledger_votes = BFTSIM_VOTES_SIGNATURES;   // what the next verify gathers (bftsim_set_ledger_votes)
     void* sig = nullptr;              // libbftsig handle (bftsig_t*)
     // the trace (bftsim_set_trace_keep, SPEC.md §11b): what bftsim_crypto_verify kept of the last launch
     bool trace_keep = false;
@@ -530,6 +534,7 @@ struct bftsim {
     std::vector<uint64_t> trace_moff, trace_ioff;   // host, [n + 1]: first message / first stream byte of each instance
     float trace_ms[3] = {0, 0, 0};    // size pass + scan, emit kernel, device-to-host copies of the last calls
     float audit_ms[4] = {0, 0, 0, 0}; // decode, recoveries, classify + tally, copies of the last audit (SPEC.md §11c)
+    float ledger_ms[4] = {0, 0, 0, 0};// decode, recoveries, tally + link, copies of the last bftsim_verify_ledger (§11d)
     uint8_t* d_tips = nullptr;        // [cap_inst * 32]
     uint32_t* d_rcs = nullptr;        // RoundChangeSet tables, rcs_words(seg) per wave / workgroup
     uint32_t* d_backlog = nullptr;    // replay mode: backlog slots, backlog_words(seg) per wave / workgroup
@@ -1884,7 +1889,8 @@ int bftsim_crypto_verify(bftsim_t* h, bftsim_crypto_report* out, uint64_t capaci
         HIPCHECK(h, hipMalloc(&h->d_vsig, vs * 65));
         HIPCHECK(h, hipMalloc(&h->d_vhas, vs));
         HIPCHECK(h, hipMemsetAsync(h->d_vhas, 0, vs, s));
-        hipLaunchKernelGGL(bft::bft_crypto_votes_kernel, dim3(g), dim3(64), 0, s, p, a, M, h->d_vsig, h->d_vhas);
+        hipLaunchKernelGGL(bft::bft_crypto_votes_kernel, dim3(g), dim3(64), 0, s, p, a, M, h->d_vsig, h->d_vhas,
+                           h->ledger_votes == BFTSIM_VOTES_SEALS ? 1u : 0u);
         HIPCHECK(h, hipGetLastError());
         h->vsig_n = n;
     }
@@ -2249,6 +2255,145 @@ int bftsim_audit_last_ms(bftsim_t* h, float* decode_ms, float* recover_ms, float
     if (recover_ms) *recover_ms = h->audit_ms[1];
     if (tally_ms) *tally_ms = h->audit_ms[2];
     if (copy_ms) *copy_ms = h->audit_ms[3];
+    return BFTSIM_OK;
+}
+
+// ---- the importer (SPEC.md §11d): every header of a ledger verified from its bytes on the device
+// votes per header (average over the slots) from which the tally takes a wave per header instead of a lane. Measured
+// at 3 votes a header (the lane mapping 2.8x faster) and at 43 (the wave mapping 8.6x faster); the
+// crossover between them was not bisected, 16 is a quarter of a wave
+static constexpr uint32_t LEDGER_WAVE_MIN_VOTES = 16;
+int bftsim_set_ledger_votes(bftsim_t* h, uint32_t kind) {
+    if (!h) return BFTSIM_EINVAL;
+    if (kind != BFTSIM_VOTES_SIGNATURES && kind != BFTSIM_VOTES_SEALS)
+        return fail(h, BFTSIM_EINVAL, "bftsim_set_ledger_votes: kind is neither BFTSIM_VOTES_SIGNATURES nor BFTSIM_VOTES_SEALS");
+    h->ledger_votes = kind;
+    return BFTSIM_OK;
+}
+
+int bftsim_verify_ledger(bftsim_t* h, const uint8_t* hdr, uint64_t slot_bytes, const uint32_t* hdr_len, uint64_t inst_count,
+                         uint32_t max_heights, const bftsim_ledger_out* out, bftsim_ledger_report* report) {
+    namespace L = bft::ledger;
+    if (!h || !report) return BFTSIM_EINVAL;
+    if (!hdr || !hdr_len) return fail(h, BFTSIM_EINVAL, "bftsim_verify_ledger: null hdr or hdr_len");
+    if (max_heights == 0 || max_heights > 65535u) return fail(h, BFTSIM_EINVAL, "bftsim_verify_ledger: max_heights outside 1..65535");
+    if (slot_bytes == 0) return fail(h, BFTSIM_EINVAL, "bftsim_verify_ledger: slot_bytes is 0");
+    if (inst_count >= (1ull << 31)) return fail(h, BFTSIM_EINVAL, "bftsim_verify_ledger: 2^31 instances or more");
+    const uint64_t slots = inst_count * max_heights, Sx = slots ? slots : 1, Ix = inst_count ? inst_count : 1;
+    // the scan's item count is an int, and a vote's header index a uint32_t
+    if (slots >= (1ull << 31) - 1) return fail(h, BFTSIM_ENOMEM, "bftsim_verify_ledger: 2^31 header slots or more");
+    if (slot_bytes > (1ull << 40) / Sx) return fail(h, BFTSIM_ENOMEM, "bftsim_verify_ledger: above 1 TiB of header slots");
+    HIPCHECK(h, hipSetDevice(h->device));
+    if (int rc = audit_sig(h)) return rc;
+    SigApi& sa = sig_api();
+    hipStream_t s = h->last_stream;
+    // the A/B switch of scripts/ledger_bench.py, read only under BFTSIM_TESTING=1: 1 lane per header, 2 wave per header
+    uint32_t mapping = 0;
+    if (const char* t = getenv("BFTSIM_TESTING"); t && strcmp(t, "1") == 0)
+        if (const char* e = getenv("BFTSIM_LEDGER_TALLY")) mapping = (uint32_t)atoi(e);
+    uint64_t bytes = 0;
+    auto sized = [&](uint64_t b) { const uint64_t o = bytes; bytes += (b + 31) & ~31ull; return o; };
+    const uint64_t o_hdr = sized(Sx * slot_bytes), o_len = sized(Sx * 4), o_recs = sized(Sx * sizeof(L::Rec)),
+                   o_vbase = sized((Sx + 1) * 8), o_voters = sized(Sx * 32), o_dup = sized(Sx * 4), o_bad = sized(Sx),
+                   o_status = sized(Sx), o_bhash = sized(Sx * 32), o_nv = sized(Sx * 2), o_vh = sized(Ix * 8),
+                   o_counts = sized(L::CNT_WORDS * 8);
+    size_t tb = 0;
+    HIPCHECK(h, hipcub::DeviceScan::ExclusiveSum(nullptr, tb, (unsigned long long*)nullptr, (unsigned long long*)nullptr,
+                                                 (int)(slots + 1)));
+    const uint64_t o_scan = sized(tb ? tb : 1);
+    DevMem pool_mem;
+    if (pool_mem.alloc(bytes) != hipSuccess)
+        return fail(h, BFTSIM_ENOMEM, "bftsim_verify_ledger: " + std::to_string(bytes) + " bytes of device memory");
+    uint8_t* pool = pool_mem.as<uint8_t>();
+    L::Args a{};
+    a.hdr = pool + o_hdr; a.hdr_len = (const uint32_t*)(pool + o_len); a.slot_bytes = slot_bytes; a.slots = slots;
+    a.inst = (uint32_t)inst_count; a.H = max_heights; a.addresses = h->d_addr; a.n = h->cfg.n;
+    a.quorum = bftsim_two_thirds_majority(h->cfg.n); a.block_period = h->cfg.block_period; a.genesis_hash = h->d_ghash;
+    a.genesis_time = h->cfg.genesis_time; a.recs = (L::Rec*)(pool + o_recs); a.vbase = (unsigned long long*)(pool + o_vbase);
+    a.voters = (uint64_t*)(pool + o_voters); a.dup = (uint32_t*)(pool + o_dup); a.bad = pool + o_bad;
+    a.status = pool + o_status; a.bhash = pool + o_bhash; a.n_votes = (uint16_t*)(pool + o_nv);
+    a.vheight = (uint64_t*)(pool + o_vh); a.counts = (unsigned long long*)(pool + o_counts);
+    Events ev, evc;
+    HIPCHECK(h, ev.create(5));
+    HIPCHECK(h, evc.create(4));
+    HIPCHECK(h, hipEventRecord(evc[0], s));
+    if (slots) {
+        HIPCHECK(h, hipMemcpyAsync(pool + o_hdr, hdr, slots * slot_bytes, hipMemcpyHostToDevice, s));
+        HIPCHECK(h, hipMemcpyAsync(pool + o_len, hdr_len, slots * 4, hipMemcpyHostToDevice, s));
+    }
+    HIPCHECK(h, hipEventRecord(evc[1], s));
+    HIPCHECK(h, hipMemsetAsync(a.counts, 0, L::CNT_WORDS * 8, s));
+    HIPCHECK(h, hipMemsetAsync(a.vbase, 0, (Sx + 1) * 8, s));
+    HIPCHECK(h, hipMemsetAsync(a.vheight, 0, Ix * 8, s));
+    // decode, then the dense vote list: a scan of the headers' vote counts, a scatter
+    unsigned long long V = 0;
+    HIPCHECK(h, hipEventRecord(ev[0], s));
+    HIPCHECK(h, L::launch_decode(a, s));
+    HIPCHECK(h, hipcub::DeviceScan::ExclusiveSum(pool + o_scan, tb, a.vbase, a.vbase, (int)(slots + 1), s));
+    HIPCHECK(h, hipEventRecord(evc[2], s));    // the host's wait for the total and its allocation are not decode time
+    HIPCHECK(h, hipMemcpyAsync(&V, a.vbase + slots, 8, hipMemcpyDeviceToHost, s));
+    HIPCHECK(h, hipStreamSynchronize(s));
+    if (V > slots * (uint64_t)L::MAX_VOTES) return fail(h, BFTSIM_EHIP, "bftsim_verify_ledger: the vote scan disagrees with the decode pass");
+    const uint64_t Vx = V ? V : 1;
+    uint64_t vbytes = 0;
+    auto vsized = [&](uint64_t b) { const uint64_t o = vbytes; vbytes += (b + 31) & ~31ull; return o; };
+    const uint64_t v_sig = vsized(Vx * 65), v_dig = vsized(Vx * 32), v_addr = vsized(Vx * 20), v_ok = vsized(Vx),
+                   v_hdr = vsized(Vx * 4);
+    DevMem vote_mem;
+    if (vote_mem.alloc(vbytes) != hipSuccess)
+        return fail(h, BFTSIM_ENOMEM, "bftsim_verify_ledger: " + std::to_string(vbytes) + " bytes of device memory for the votes");
+    uint8_t* vp = vote_mem.as<uint8_t>();
+    a.votes = V; a.vsig = vp + v_sig; a.vdig = vp + v_dig; a.vaddr = vp + v_addr; a.vok = vp + v_ok;
+    a.vhdr = (uint32_t*)(vp + v_hdr);
+    HIPCHECK(h, hipEventRecord(evc[3], s));
+    HIPCHECK(h, L::launch_scatter(a, s));
+    HIPCHECK(h, hipEventRecord(ev[1], s));
+    // recoveries: every vote over its header's seal digest
+    if (V && sa.recover(h->sig, a.vdig, a.vsig, V, nullptr, a.vaddr, a.vok, s) != 0)
+        return fail(h, BFTSIM_EHIP, std::string("bftsig_recover: ") + sa.last_error(h->sig));
+    HIPCHECK(h, hipEventRecord(ev[2], s));
+    // a lane per header below this many votes per header on average, a wave per header from there
+    if (mapping != L::TALLY_LANE && mapping != L::TALLY_WAVE)
+        mapping = V < slots * (uint64_t)LEDGER_WAVE_MIN_VOTES ? L::TALLY_LANE : L::TALLY_WAVE;
+    HIPCHECK(h, L::launch_tally(a, mapping, s));
+    HIPCHECK(h, L::launch_link(a, s));
+    HIPCHECK(h, hipEventRecord(ev[3], s));
+    unsigned long long c[L::CNT_WORDS] = {0};
+    HIPCHECK(h, hipMemcpyAsync(c, a.counts, sizeof c, hipMemcpyDeviceToHost, s));
+    HIPCHECK(h, hipStreamSynchronize(s));      // every pass succeeded: only now the caller's buffers
+    if (out) {
+        const struct { void* dst; uint64_t off, b; } back[] = {
+            {out->status, o_status, slots}, {out->block_hash, o_bhash, slots * 32}, {out->voters, o_voters, slots * 32},
+            {out->n_votes, o_nv, slots * 2}, {out->verified_height, o_vh, inst_count * 8}};
+        for (const auto& k : back)
+            if (k.dst && k.b) HIPCHECK(h, hipMemcpyAsync(k.dst, pool + k.off, k.b, hipMemcpyDeviceToHost, s));
+    }
+    HIPCHECK(h, hipEventRecord(ev[4], s));
+    HIPCHECK(h, hipStreamSynchronize(s));
+    float ms[4] = {0, 0, 0, 0}, in_ms = 0;
+    for (int k = 0; k < 4; ++k) HIPCHECK(h, hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]));
+    HIPCHECK(h, hipEventElapsedTime(&in_ms, evc[0], evc[1]));
+    float scan_ms = 0, scatter_ms = 0;
+    HIPCHECK(h, hipEventElapsedTime(&scan_ms, ev[0], evc[2]));
+    HIPCHECK(h, hipEventElapsedTime(&scatter_ms, evc[3], ev[1]));
+    ms[0] = scan_ms + scatter_ms;              // decode kernel + scan, then the scatter: device time on either side of the wait
+    h->ledger_ms[0] = ms[0]; h->ledger_ms[1] = ms[1]; h->ledger_ms[2] = ms[2]; h->ledger_ms[3] = ms[3] + in_ms;
+    memset(report, 0, sizeof *report);
+    report->headers = c[L::CNT_HEADERS];
+    for (uint32_t k = 0; k < L::ST_COUNT; ++k) report->by_status[k] = c[L::CNT_STATUS + k];
+    report->votes = V;
+    report->recoveries = V;
+    report->duplicate_votes = c[L::CNT_DUP];
+    report->verified_instances = c[L::CNT_WHOLE];
+    return BFTSIM_OK;
+}
+
+int bftsim_ledger_last_ms(bftsim_t* h, float* decode_ms, float* recover_ms, float* tally_ms, float* copy_ms) {
+    if (!h) return BFTSIM_EINVAL;
+    if (decode_ms) *decode_ms = h->ledger_ms[0];
+    if (recover_ms) *recover_ms = h->ledger_ms[1];
+    if (tally_ms) *tally_ms = h->ledger_ms[2];
+    if (copy_ms) *copy_ms = h->ledger_ms[3];
     return BFTSIM_OK;
 }
 

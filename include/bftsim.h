@@ -233,7 +233,8 @@ int bftsim_crypto_verify(bftsim_t *h, bftsim_crypto_report *out, uint64_t capaci
  * x <= committed_height, in slot [i*H + x-1] of `slot_bytes` bytes, the Header that Backend::commit
  * inserts (backend.rs:163-174): the block's header (SPEC.md §7) with votes = the signatures of the
  * Commit messages in the committing Core's commit set at its commit (core.rs:402-413), ascending
- * validator order. hdr_len = 0 beyond the committed height. The hash of a header is the run's
+ * validator order (or, after bftsim_set_ledger_votes(h, BFTSIM_VOTES_SEALS), those Commits' seals: the votes that
+ * bftsim_verify_ledger can check). hdr_len = 0 beyond the committed height. The hash of a header is the run's
  * block_hash of that height (block_hash() ignores votes, types/block.rs:76-80). Together with
  * block_hash per height this is the ledger's headers + block_hashes_by_height (store/schema.rs). */
 uint64_t bftsim_ledger_slot_bytes(uint32_t n_validators);
@@ -333,6 +334,68 @@ int bftsim_audit_last_trace(bftsim_t *h, uint64_t inst_begin, uint64_t inst_coun
 /* diagnostics: device times (ms, HIP events) of the last audit's decode kernel, recoveries, classification + tally, and
  * copies (the stream to the device, the outputs back), as scripts/audit_bench.py records them */
 int bftsim_audit_last_ms(bftsim_t *h, float *decode_ms, float *recover_ms, float *tally_ms, float *copy_ms);
+
+/* the importer (SPEC.md §11d): what a syncing node runs on every Header it is handed, Engine::verify_header with
+ * seal = true and verify_seal (src/consensus/backend.rs:319-367), batched: every header of every instance's ledger,
+ * verified from untrusted bytes on the device.
+ * A vote that can be verified from its header is a commit seal, sign(keccak(0x03 || block hash)) (types/votes.rs:68-101):
+ * it depends on the block alone. The reference's Core::commit hands Backend::commit the Commit messages' signatures
+ * instead (core.rs:402-413), whose payload holds a round and a seal that the header does not carry. So the votes the
+ * ledger keeps are a switch, read by the next bftsim_crypto_verify (which gathers them; still one 65-byte table): */
+#define BFTSIM_VOTES_SIGNATURES 0u     /* the Commit messages' signatures, as the reference stores them (default) */
+#define BFTSIM_VOTES_SEALS 1u          /* the Commits' seals, a.k.a. what verify_seal recovers */
+/* any other kind is BFTSIM_EINVAL; slot layout, order and bftsim_ledger_slot_bytes of bftsim_export_ledger are the same */
+int bftsim_set_ledger_votes(bftsim_t *h, uint32_t kind);
+/* header status (one byte per slot). The checks run in the reference's order and the first that fails wins; verify_seal
+ * checks its votes' signatures before it counts them, so BAD_VOTE is decided before the LACK_VOTES of too few voters: */
+#define BFTSIM_LEDGER_OK 0u            /* every check below passes */
+#define BFTSIM_LEDGER_ABSENT 1u        /* hdr_len = 0 */
+#define BFTSIM_LEDGER_UNDECODABLE 2u   /* hdr_len > slot_bytes (nothing is read); not a SPEC.md §7 Header of 11..13 fields
+                                          (extra above 32 bytes included) or trailing bytes; a vote that is not 65 bytes;
+                                          more than 256 votes */
+#define BFTSIM_LEDGER_BAD_HEIGHT 3u    /* header.height is 0 (InvalidHeight) or is not the slot's x */
+#define BFTSIM_LEDGER_NO_PARENT 4u     /* x > 1 and slot x - 1 is ABSENT or UNDECODABLE (UnknownAncestor) */
+#define BFTSIM_LEDGER_BAD_PARENT 5u    /* prev_hash != the parent's block hash */
+#define BFTSIM_LEDGER_BAD_TIME 6u      /* time < parent.time + block_period (InvalidTimestamp) */
+#define BFTSIM_LEDGER_LACK_VOTES 7u    /* votes None or fewer than 13 fields; or, after BAD_VOTE, distinct voters <=
+                                          bftsim_two_thirds_majority(N) (LackVotes) */
+#define BFTSIM_LEDGER_BAD_VOTE 8u      /* a vote does not recover, or recovers outside the set (InvalidSignature) */
+#define BFTSIM_LEDGER_BAD_PROPOSER 9u  /* header.proposer is not in the set */
+struct bftsim_ledger_report {
+    uint64_t headers;               /* slots with hdr_len != 0 */
+    uint64_t by_status[10];         /* slots per status, ABSENT included */
+    uint64_t votes;                 /* votes of the decodable headers */
+    uint64_t recoveries;            /* ECDSA recoveries performed (one per vote) */
+    uint64_t duplicate_votes;       /* votes of a validator whose vote the header already held (not counted as voters) */
+    uint64_t verified_instances;    /* instances where every non-absent slot is OK and the absent ones form a suffix */
+};
+typedef struct bftsim_ledger_report bftsim_ledger_report;
+struct bftsim_ledger_out {          /* host, caller-owned, any pointer may be NULL; rows inst * max_heights + x - 1 */
+    uint8_t *status;                /* [inst_count * max_heights] BFTSIM_LEDGER_* */
+    uint8_t *block_hash;            /* x32: Keccak-256 of the header re-encoded from its decoded fields with votes nil
+                                       (deserialize, then block_hash()); zeros where absent or undecodable */
+    uint64_t *voters;               /* x4: bitmap of the validators whose seal recovered */
+    uint16_t *n_votes;              /* votes the header carries (0 where None, absent or undecodable) */
+    uint64_t *verified_height;      /* [inst_count] the largest x with slots 1..x all OK */
+};
+typedef struct bftsim_ledger_out bftsim_ledger_out;
+/* hdr / hdr_len: host buffers in the layout bftsim_export_ledger writes (slot i * max_heights + x - 1 of slot_bytes
+ * bytes, hdr_len 0 for an absent height). The parent of x = 1 is the genesis (bftsim_genesis_hash, genesis_time); the
+ * parent of x > 1 is slot x - 1 as decoded, whether or not it verified itself. A vote is recovered over
+ * keccak(0x03 || block hash). The reference counts votes.len(); distinct validators are counted here (a validator's
+ * seal is the same bytes every time, RFC 6979), the surplus reported in duplicate_votes. The validator set, N,
+ * block_period, genesis_time and the genesis hash are the handle's; no secrets are needed and bftsim_set_crypto need
+ * not have been called (libbftsig.so must be next to libbftsim.so). The handle's run state is untouched; the work runs
+ * on the stream of the last launch (the default stream when there is none). Arguments are checked before any device
+ * work and a refused call writes nothing: BFTSIM_EINVAL for a null h, hdr, hdr_len or report, max_heights of 0 or above
+ * 65,535, slot_bytes of 0, 2^31 instances or more; BFTSIM_ENOMEM for 2^31 slots or more. Hostile contents are never an
+ * error of the call: they become statuses. */
+int bftsim_verify_ledger(bftsim_t *h, const uint8_t *hdr, uint64_t slot_bytes, const uint32_t *hdr_len,
+                         uint64_t inst_count, uint32_t max_heights, const bftsim_ledger_out *out,
+                         bftsim_ledger_report *report);
+/* diagnostics: device times (ms, HIP events) of the last bftsim_verify_ledger's decode (the decode kernel and the vote
+ * scan, then the scatter; not the host's wait for the scan's total between them), recoveries, tally + link, and copies, as scripts/ledger_bench.py records them */
+int bftsim_ledger_last_ms(bftsim_t *h, float *decode_ms, float *recover_ms, float *tally_ms, float *copy_ms);
 
 /* ValidatorSet / block helpers on the host (validator.rs, types/block.rs) */
 uint32_t bftsim_two_thirds_majority(uint32_t n);                    /* validator.rs:149-154 */
