@@ -62,6 +62,27 @@ class CLedgerOut(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in ("status", "block_hash", "voters", "n_votes", "verified_height")]
 
 
+class CArchiveReport(ctypes.Structure):
+    _fields_ = [("headers", ctypes.c_uint64), ("by_status", ctypes.c_uint64 * 3)] + [(k, ctypes.c_uint64) for k in (
+        "votes", "foreign_seals", "archived_instances")]
+
+
+class CArchiveOut(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in ("status", "pp_frame", "n_votes", "archived_height")]
+
+
+def alloc_archive(n_inst: int, heights: int, slot_bytes: int):
+    """host buffers of bftsim_archive_trace: the header slots, their lengths and bftsim_archive_out -> (hdr, hdr_len,
+    struct, arrays)"""
+    rows = n_inst * heights
+    arrs = dict(status=np.full(rows, 1, np.uint8), pp_frame=np.full(rows, 0xffffffff, np.uint32),
+                n_votes=np.zeros(rows, np.uint16), archived_height=np.zeros(n_inst, np.uint64))
+    o = CArchiveOut()
+    for k, a in arrs.items():
+        setattr(o, k, a.ctypes.data)
+    return np.zeros(rows * slot_bytes, np.uint8), np.zeros(rows, np.uint32), o, arrs
+
+
 def alloc_ledger(n_inst: int, heights: int):
     """host buffers of bftsim_ledger_out -> (struct, arrays)"""
     rows = n_inst * heights

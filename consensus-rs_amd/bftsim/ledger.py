@@ -54,6 +54,36 @@ class Verdict:
         return [STATUS_NAMES[int(s)] for s in self.status[i]]
 
 
+AR_OK, AR_NONE, AR_NO_PROPOSAL = range(3)
+ARCHIVE_NAMES = ("OK", "NONE", "NO_PROPOSAL")
+
+
+class Archive:
+    """What the archiver says of the ledger it wrote (bftsim_archive_trace, SPEC.md §11e): status [n, H] u8 (AR_*),
+    pp_frame [n, H] u32 (the PrePrepare frame a header was taken from, index within its instance; 0xffffffff if none),
+    n_votes [n, H] u16 (seals in the slot), archived_height [n] u64 (the largest x with slots 1..x all OK); report:
+    bftsim_archive_report as a dict; audit: the observer's bftsim.trace.Audit of the same call."""
+
+    def __init__(self, arrs: dict, rep, n: int, heights: int, audit=None):
+        self.n, self.heights, self.audit = n, heights, audit
+        self.status = arrs["status"].reshape(n, heights)
+        self.pp_frame = arrs["pp_frame"].reshape(n, heights)
+        self.n_votes = arrs["n_votes"].reshape(n, heights)
+        self.archived_height = arrs["archived_height"]
+        self.report = rep if isinstance(rep, dict) else {
+            k: (list(getattr(rep, k)) if k == "by_status" else int(getattr(rep, k))) for k, _ in rep._fields_}
+
+    def names(self, i: int) -> list:
+        return [ARCHIVE_NAMES[int(s)] for s in self.status[i]]
+
+
+def unpack(ledger):
+    """(hdr, hdr_len, slot_bytes, heights) -> per instance the list of header byte strings, b"" for an absent height"""
+    hdr, lens, slot, H = ledger
+    hdr, lens = np.asarray(hdr, np.uint8).reshape(-1, slot), np.asarray(lens, np.uint32).reshape(-1, H)
+    return [[bytes(hdr[i * H + x, :int(lens[i, x])]) for x in range(H)] for i in range(lens.shape[0])]
+
+
 def compare(verdict: Verdict, result: dict, begin: int = 0) -> dict:
     """The verdict against a run's result (Simulator.run / fetch; verdict instance i = result instance begin + i). Per
     instance, over the committed heights: `ok` headers that verify, `same_hash` whose block hash is the run's;

@@ -75,6 +75,11 @@ def lib():
         L.bftsim_audit_last_trace.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32,
                                               ctypes.POINTER(_abi.CAuditOut), ctypes.POINTER(_abi.CAuditReport)]
         L.bftsim_audit_last_ms.argtypes = [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_float)] * 4
+        tail = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.POINTER(_abi.CArchiveOut),
+                ctypes.POINTER(_abi.CAuditOut), ctypes.POINTER(_abi.CAuditReport), ctypes.POINTER(_abi.CArchiveReport)]
+        L.bftsim_archive_trace.argtypes = L.bftsim_audit_trace.argtypes[:9] + tail
+        L.bftsim_archive_last_trace.argtypes = L.bftsim_audit_last_trace.argtypes[:4] + tail
+        L.bftsim_archive_last_ms.argtypes = [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_float)] * 4
         L.bftsim_set_ledger_votes.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
         L.bftsim_verify_ledger.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
                                            ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(_abi.CLedgerOut),
@@ -397,6 +402,56 @@ class Simulator:
         """(decode, recoveries, classify + tally, copies) of the last audit, device ms (bftsim_audit_last_ms)."""
         v = [ctypes.c_float() for _ in range(4)]
         _check(self.h, lib().bftsim_audit_last_ms(self.h, *[ctypes.byref(x) for x in v]), "bftsim_audit_last_ms")
+        return tuple(x.value for x in v)
+
+    def archive_trace(self, trace, max_heights: int = None, key_cap: int = 0):
+        """The archiver (include/bftsim.h bftsim_archive_trace, SPEC.md §11e) over a bftsim.trace.Trace, or anything with
+        its stream / frame_off / inst_frame0: the ledger of the heights the observer certifies, each header assembled on
+        the device from the PrePrepare frame's block and the voters' commit seals. -> (ledger, bftsim.ledger.Archive);
+        ledger is the (hdr, hdr_len, slot_bytes, heights) that verify_ledger takes."""
+        from .ledger import Archive
+        from .trace import Audit
+        H = self.cfg.heights if max_heights is None else max_heights
+        stream = np.ascontiguousarray(trace.stream, np.uint8)
+        off = np.ascontiguousarray(trace.frame_off, np.uint64)
+        f0 = np.ascontiguousarray(trace.inst_frame0, np.uint64)
+        frames, n = len(off) - 1, len(f0) - 1
+        ok = 0 < H <= 65535                        # the library refuses it; no buffers are sized by it here
+        slot = lib().bftsim_ledger_slot_bytes(self.cfg.n)
+        hdr, lens, o, arrs = _abi.alloc_archive(n, H if ok else 0, slot)
+        ao, aarrs = _abi.alloc_audit(frames, n, H if ok else 0)
+        rep, arep = _abi.CArchiveReport(), _abi.CAuditReport()
+        _check(self.h, lib().bftsim_archive_trace(self.h, stream.ctypes.data, len(stream), off.ctypes.data, frames,
+                                                  f0.ctypes.data, n, H, key_cap, hdr.ctypes.data, slot, lens.ctypes.data,
+                                                  ctypes.byref(o), ctypes.byref(ao), ctypes.byref(arep), ctypes.byref(rep)),
+               "bftsim_archive_trace")
+        return (hdr, lens, slot, H), Archive(arrs, rep, n, H, Audit(aarrs, arep, n, H))
+
+    def archive_last_trace(self, begin: int = 0, count: int = None, key_cap: int = 0):
+        """The same over the kept trace of the last launch (after crypto_verify with set_trace_keep), instances
+        [begin, begin + count): emitted, audited and archived on the device (bftsim_archive_last_trace)."""
+        from .ledger import Archive
+        from .trace import Audit
+        if count is None:
+            count = self.n_launched - begin
+        fr, _ = self.trace_sizes()
+        if begin < 0 or count < 0 or begin + count > len(fr):
+            raise BftsimError(f"archive_last_trace: instances [{begin}, {begin + count}) outside the last launch of {len(fr)}")
+        H = self.cfg.heights
+        slot = lib().bftsim_ledger_slot_bytes(self.cfg.n)
+        hdr, lens, o, arrs = _abi.alloc_archive(count, H, slot)
+        ao, aarrs = _abi.alloc_audit(int(fr[begin:begin + count].sum()), count, H)
+        rep, arep = _abi.CArchiveReport(), _abi.CAuditReport()
+        _check(self.h, lib().bftsim_archive_last_trace(self.h, begin, count, key_cap, hdr.ctypes.data, slot, lens.ctypes.data,
+                                                       ctypes.byref(o), ctypes.byref(ao), ctypes.byref(arep), ctypes.byref(rep)),
+               "bftsim_archive_last_trace")
+        return (hdr, lens, slot, H), Archive(arrs, rep, count, H, Audit(aarrs, arep, count, H))
+
+    def archive_ms(self):
+        """(the observer's passes, pick, emit + heights, copies) of the last archive call, device ms
+        (bftsim_archive_last_ms)."""
+        v = [ctypes.c_float() for _ in range(4)]
+        _check(self.h, lib().bftsim_archive_last_ms(self.h, *[ctypes.byref(x) for x in v]), "bftsim_archive_last_ms")
         return tuple(x.value for x in v)
 
     def set_ledger_votes(self, kind: str):

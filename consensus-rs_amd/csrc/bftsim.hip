@@ -30,6 +30,7 @@
 #include "bft_crypto.h"
 #include "bft_trace.h"
 #include "bft_audit.h"
+#include "bft_archive.h"
 #include "bft_ledger.h"
 
 namespace bft {
@@ -642,6 +643,7 @@ struct bftsim {
     uint32_t ring_head = 0;
     double acc_c = 0, acc_h = 0;
     uint32_t acc_n = 0;
+    float archive_ms[4] = {0, 0, 0, 0};// the observer's passes, pick, emit + heights, copies of the last archive (SPEC.md §11e)
 };
 
 static int fail(bftsim* h, int code, const std::string& msg) {
@@ -2092,11 +2094,100 @@ static int audit_sig(bftsim* h) {
     if (!h->sig && a.create(h->device, &h->sig) != 0) return fail(h, BFTSIM_EHIP, "bftsig_create failed");
     return BFTSIM_OK;
 }
+// ---- the archiver (SPEC.md §11e): a continuation of audit_device, run after the tally while the pool is alive. Its
+// tables and header slots are one more piece of the pool; the observer's two entry points pass none.
+namespace {
+struct ArchiveCont {
+    uint8_t* hdr;                     // the caller's
+    uint64_t slot_bytes;
+    uint32_t* hdr_len;
+    const bftsim_archive_out* out;
+    bftsim_archive_report* report;
+    // the piece's layout (archive_layout): the device slot is the smallest the boundary admits
+    uint64_t dslot, bytes, o_pick, o_hdr, o_len, o_status, o_pp, o_nv, o_nf, o_height, o_counts;
+    unsigned long long counts[bft::archive::CNT_WORDS];
+    float ms[2];                      // pick, emit + heights
+};
+}  // namespace
+static int archive_layout(bftsim* h, ArchiveCont& ac, uint64_t inst, uint32_t max_heights) {
+    namespace R = bft::archive;
+    const uint64_t rows = inst * max_heights, Rx = rows ? rows : 1, Ix = inst ? inst : 1;
+    if (rows >= (1ull << 31) - 1) return fail(h, BFTSIM_ENOMEM, "bftsim_archive: 2^31 header slots or more");
+    ac.dslot = bftsim_ledger_slot_bytes(h->cfg.n);
+    uint64_t bytes = 0;
+    auto sized = [&](uint64_t b) { const uint64_t o = bytes; bytes += (b + 31) & ~31ull; return o; };
+    ac.o_pick = sized(Rx * R::pick_words(bftsim_two_thirds_majority(h->cfg.n)) * 4);
+    ac.o_hdr = sized(Rx * ac.dslot);
+    ac.o_len = sized(Rx * 4); ac.o_status = sized(Rx); ac.o_pp = sized(Rx * 4); ac.o_nv = sized(Rx * 2); ac.o_nf = sized(Rx * 2);
+    ac.o_height = sized(Ix * 8); ac.o_counts = sized(R::CNT_WORDS * 8);
+    ac.bytes = bytes;
+    return BFTSIM_OK;
+}
+static int archive_passes(bftsim* h, ArchiveCont& ac, uint8_t* p, const uint8_t* d_stream, const uint64_t* d_foff, uint64_t base,
+                          uint64_t frames, const bft::audit::Recs& r, const uint8_t* d_status, const int32_t* d_signer,
+                          const uint64_t* d_if0, uint64_t inst, uint32_t max_heights, const bft::archive::Certs& certs,
+                          hipStream_t s) {
+    namespace R = bft::archive;
+    const R::Args a{d_stream, d_foff, base, frames, r, d_status, d_signer, d_if0, inst, max_heights,
+                    bftsim_two_thirds_majority(h->cfg.n), certs, (uint32_t*)(p + ac.o_pick), p + ac.o_hdr, ac.dslot,
+                    (uint32_t*)(p + ac.o_len), p + ac.o_status, (uint32_t*)(p + ac.o_pp), (uint16_t*)(p + ac.o_nv),
+                    (uint16_t*)(p + ac.o_nf), (uint64_t*)(p + ac.o_height), (unsigned long long*)(p + ac.o_counts)};
+    Events ev;
+    HIPCHECK(h, ev.create(3));
+    HIPCHECK(h, hipMemsetAsync(p + ac.o_pick, 0xff, ac.o_hdr - ac.o_pick, s));        // NONE
+    HIPCHECK(h, hipMemsetAsync(p + ac.o_hdr, 0, ac.bytes - ac.o_hdr, s));             // the slots' tails, the counters
+    HIPCHECK(h, hipEventRecord(ev[0], s));
+    HIPCHECK(h, R::launch_pick(a, s));
+    HIPCHECK(h, hipEventRecord(ev[1], s));
+    HIPCHECK(h, R::launch_emit(a, s));
+    HIPCHECK(h, R::launch_heights(a, s));
+    HIPCHECK(h, hipEventRecord(ev[2], s));
+    HIPCHECK(h, hipMemcpyAsync(ac.counts, p + ac.o_counts, sizeof ac.counts, hipMemcpyDeviceToHost, s));
+    HIPCHECK(h, hipStreamSynchronize(s));
+    for (int k = 0; k < 2; ++k) HIPCHECK(h, hipEventElapsedTime(&ac.ms[k], ev[k], ev[k + 1]));
+    if (ac.counts[R::CNT_ERR])     // a header above its slot, or an emit pass that disagrees with the pick pass
+        return fail(h, BFTSIM_EHIP, "bftsim_archive: " + std::to_string(ac.counts[R::CNT_ERR]) +
+                                        " headers did not fit their slot or lost a picked frame");
+    return BFTSIM_OK;
+}
+static int archive_copy(bftsim* h, ArchiveCont& ac, const uint8_t* p, uint64_t inst, uint32_t max_heights, hipStream_t s) {
+    namespace R = bft::archive;
+    const uint64_t rows = inst * max_heights;
+    Events ev;
+    HIPCHECK(h, ev.create(2));
+    HIPCHECK(h, hipEventRecord(ev[0], s));
+    if (rows) {
+        HIPCHECK(h, hipMemcpy2DAsync(ac.hdr, ac.slot_bytes, p + ac.o_hdr, ac.dslot, ac.dslot, rows, hipMemcpyDeviceToHost, s));
+        HIPCHECK(h, hipMemcpyAsync(ac.hdr_len, p + ac.o_len, rows * 4, hipMemcpyDeviceToHost, s));
+    }
+    if (ac.out) {
+        const struct { void* dst; uint64_t off, b; } back[] = {
+            {ac.out->status, ac.o_status, rows}, {ac.out->pp_frame, ac.o_pp, rows * 4}, {ac.out->n_votes, ac.o_nv, rows * 2},
+            {ac.out->archived_height, ac.o_height, inst * 8}};
+        for (const auto& k : back)
+            if (k.dst && k.b) HIPCHECK(h, hipMemcpyAsync(k.dst, p + k.off, k.b, hipMemcpyDeviceToHost, s));
+    }
+    HIPCHECK(h, hipEventRecord(ev[1], s));
+    HIPCHECK(h, hipStreamSynchronize(s));
+    float copy_ms = 0;
+    HIPCHECK(h, hipEventElapsedTime(&copy_ms, ev[0], ev[1]));
+    h->archive_ms[0] = h->audit_ms[0] + h->audit_ms[1] + h->audit_ms[2];
+    h->archive_ms[1] = ac.ms[0]; h->archive_ms[2] = ac.ms[1]; h->archive_ms[3] = h->audit_ms[3] + copy_ms;
+    bftsim_archive_report* rep = ac.report;
+    memset(rep, 0, sizeof *rep);
+    rep->headers = ac.counts[R::CNT_STATUS + R::AR_OK];
+    for (int k = 0; k < 3; ++k) rep->by_status[k] = ac.counts[R::CNT_STATUS + k];
+    rep->votes = ac.counts[R::CNT_VOTES];
+    rep->foreign_seals = ac.counts[R::CNT_FOREIGN];
+    rep->archived_instances = ac.counts[R::CNT_ARCHIVED];
+    return BFTSIM_OK;
+}
 // the passes over a device stream: frame k = d_stream[d_foff[k] - base, d_foff[k + 1] - base),
 // if0 on the host. Every temporary is freed before returning; only the caller's buffers and h->audit_ms are written.
 static int audit_device(bftsim* h, const uint8_t* d_stream, const uint64_t* d_foff, uint64_t base, uint64_t frames,
                         const uint64_t* if0, uint64_t inst, uint32_t max_heights, uint32_t key_cap,
-                        const bftsim_audit_out* out, bftsim_audit_report* report, hipStream_t s, float copy_in_ms) {
+                        const bftsim_audit_out* out, bftsim_audit_report* report, hipStream_t s, float copy_in_ms,
+                        ArchiveCont* ac = nullptr) {
     namespace A = bft::audit;
     SigApi& sa = sig_api();
     if (key_cap == 0) key_cap = 4u * max_heights + 64u;
@@ -2112,6 +2203,11 @@ static int audit_device(bftsim* h, const uint8_t* d_stream, const uint64_t* d_fo
                    o_if0 = sized((inst + 1) * 8), o_keys = sized(Ix * key_cap * sizeof(A::Key)), o_iflags = sized(Ix * 4),
                    o_cround = sized(Rx * 2), o_cdig = sized(Rx * 32), o_cvot = sized(Rx * 32), o_cframe = sized(Rx * 4),
                    o_cflags = sized(Rx), o_counts = sized(A::CNT_WORDS * 8), o_nseal = sized(4);
+    const uint64_t o_arch = bytes;
+    if (ac) {                                                                      // the archiver's tables and slots
+        if (int rc = archive_layout(h, *ac, inst, max_heights)) return rc;
+        bytes += ac->bytes;
+    }
     DevMem pool_mem;
     if (pool_mem.alloc(bytes) != hipSuccess)
         return fail(h, BFTSIM_ENOMEM, "bftsim_audit: " + std::to_string(bytes) + " bytes of device memory");
@@ -2155,6 +2251,13 @@ static int audit_device(bftsim* h, const uint8_t* d_stream, const uint64_t* d_fo
     unsigned long long c[A::CNT_WORDS] = {0};
     HIPCHECK(h, hipMemcpyAsync(c, d_counts, sizeof c, hipMemcpyDeviceToHost, s));
     HIPCHECK(h, hipStreamSynchronize(s));      // every pass succeeded: only now the caller's buffers
+    if (ac) {
+        const bft::archive::Certs certs{(const uint16_t*)(pool + o_cround), pool + o_cdig, (const uint64_t*)(pool + o_cvot),
+                                        (const uint32_t*)(pool + o_cframe)};
+        if (int rc = archive_passes(h, *ac, pool + o_arch, d_stream, d_foff, base, F, r, d_status, d_signer, d_if0, inst,
+                                    max_heights, certs, s))
+            return rc;
+    }
     if (out) {
         const struct { void* dst; uint64_t off, b; } back[] = {
             {out->frame_status, o_status, F}, {out->frame_signer, o_signer, F * 4}, {out->inst_flags, o_iflags, inst * 4},
@@ -2179,7 +2282,7 @@ static int audit_device(bftsim* h, const uint8_t* d_stream, const uint64_t* d_fo
     report->conflicts = c[A::CNT_CONFLICTS];
     report->key_overflows = c[A::CNT_KEY_OVERFLOWS];
     report->recoveries = F + n_seals;
-    return BFTSIM_OK;
+    return ac ? archive_copy(h, *ac, pool + o_arch, inst, max_heights, s) : BFTSIM_OK;
 }
 static int audit_dims(bftsim* h, uint64_t frames, uint64_t inst, uint32_t max_heights, const char* what) {
     if (max_heights == 0 || max_heights > 65535u) return fail(h, BFTSIM_EINVAL, std::string(what) + ": max_heights outside 1..65535");
@@ -2188,10 +2291,10 @@ static int audit_dims(bftsim* h, uint64_t frames, uint64_t inst, uint32_t max_he
     return BFTSIM_OK;
 }
 
-int bftsim_audit_trace(bftsim_t* h, const uint8_t* stream, uint64_t stream_bytes, const uint64_t* frame_off, uint64_t frames,
-                       const uint64_t* inst_frame0, uint64_t inst_count, uint32_t max_heights, uint32_t key_cap,
-                       const bftsim_audit_out* out, bftsim_audit_report* report) {
-    if (!h || !report) return BFTSIM_EINVAL;
+// the observer over a host stream; ac: the archiver's continuation (null for bftsim_audit_trace)
+static int audit_host_stream(bftsim* h, const uint8_t* stream, uint64_t stream_bytes, const uint64_t* frame_off, uint64_t frames,
+                             const uint64_t* inst_frame0, uint64_t inst_count, uint32_t max_heights, uint32_t key_cap,
+                             const bftsim_audit_out* out, bftsim_audit_report* report, ArchiveCont* ac) {
     if (!frame_off || !inst_frame0 || (stream_bytes && !stream))
         return fail(h, BFTSIM_EINVAL, "bftsim_audit_trace: null stream, frame_off or inst_frame0");
     if (int rc = audit_dims(h, frames, inst_count, max_heights, "bftsim_audit_trace")) return rc;
@@ -2220,12 +2323,19 @@ int bftsim_audit_trace(bftsim_t* h, const uint8_t* stream, uint64_t stream_bytes
     HIPCHECK(h, hipStreamSynchronize(s));
     HIPCHECK(h, hipEventElapsedTime(&copy_ms, ev[0], ev[1]));
     return audit_device(h, d_in, (const uint64_t*)(d_in + sb + 16), 0, frames, inst_frame0, inst_count, max_heights, key_cap,
-                        out, report, s, copy_ms);
+                        out, report, s, copy_ms, ac);
+}
+int bftsim_audit_trace(bftsim_t* h, const uint8_t* stream, uint64_t stream_bytes, const uint64_t* frame_off, uint64_t frames,
+                       const uint64_t* inst_frame0, uint64_t inst_count, uint32_t max_heights, uint32_t key_cap,
+                       const bftsim_audit_out* out, bftsim_audit_report* report) {
+    if (!h || !report) return BFTSIM_EINVAL;
+    return audit_host_stream(h, stream, stream_bytes, frame_off, frames, inst_frame0, inst_count, max_heights, key_cap, out,
+                             report, nullptr);
 }
 
-int bftsim_audit_last_trace(bftsim_t* h, uint64_t inst_begin, uint64_t inst_count, uint32_t key_cap,
-                            const bftsim_audit_out* out, bftsim_audit_report* report) {
-    if (!h || !report) return BFTSIM_EINVAL;
+// the observer over the kept trace of the last launch; ac as above
+static int audit_kept_trace(bftsim* h, uint64_t inst_begin, uint64_t inst_count, uint32_t key_cap,
+                            const bftsim_audit_out* out, bftsim_audit_report* report, ArchiveCont* ac) {
     if (int rc = trace_ready(h, "bftsim_audit_last_trace")) return rc;
     const uint64_t n = h->trace_n;
     if (inst_begin > n || inst_count > n - inst_begin)
@@ -2246,7 +2356,12 @@ int bftsim_audit_last_trace(bftsim_t* h, uint64_t inst_begin, uint64_t inst_coun
         return fail(h, BFTSIM_ENOMEM, "bftsim_audit_last_trace: device memory for the stream");
     if (int rc = trace_emit(h, "bftsim_audit_last_trace", m0, m1, d_out.as<uint8_t>(), nullptr, nullptr)) return rc;
     return audit_device(h, d_out.as<uint8_t>(), h->d_tfoff + m0, base, frames, if0.data(), inst_count, h->cfg.heights,
-                        key_cap, out, report, s, 0.f);
+                        key_cap, out, report, s, 0.f, ac);
+}
+int bftsim_audit_last_trace(bftsim_t* h, uint64_t inst_begin, uint64_t inst_count, uint32_t key_cap,
+                            const bftsim_audit_out* out, bftsim_audit_report* report) {
+    if (!h || !report) return BFTSIM_EINVAL;
+    return audit_kept_trace(h, inst_begin, inst_count, key_cap, out, report, nullptr);
 }
 
 int bftsim_audit_last_ms(bftsim_t* h, float* decode_ms, float* recover_ms, float* tally_ms, float* copy_ms) {
@@ -2255,6 +2370,44 @@ int bftsim_audit_last_ms(bftsim_t* h, float* decode_ms, float* recover_ms, float
     if (recover_ms) *recover_ms = h->audit_ms[1];
     if (tally_ms) *tally_ms = h->audit_ms[2];
     if (copy_ms) *copy_ms = h->audit_ms[3];
+    return BFTSIM_OK;
+}
+
+// ---- the archiver's entry points (SPEC.md §11e): the observer's passes and refusals, then pick, emit and heights
+static int archive_args(bftsim* h, uint8_t* hdr, uint64_t slot_bytes, uint32_t* hdr_len, const char* what) {
+    if (!hdr || !hdr_len) return fail(h, BFTSIM_EINVAL, std::string(what) + ": null hdr or hdr_len");
+    if (slot_bytes < bftsim_ledger_slot_bytes(h->cfg.n)) return fail(h, BFTSIM_EINVAL, std::string(what) + ": slot_bytes too small");
+    return BFTSIM_OK;
+}
+int bftsim_archive_trace(bftsim_t* h, const uint8_t* stream, uint64_t stream_bytes, const uint64_t* frame_off, uint64_t frames,
+                         const uint64_t* inst_frame0, uint64_t inst_count, uint32_t max_heights, uint32_t key_cap,
+                         uint8_t* hdr, uint64_t slot_bytes, uint32_t* hdr_len, const bftsim_archive_out* out,
+                         const bftsim_audit_out* audit_out, bftsim_audit_report* audit_report, bftsim_archive_report* report) {
+    if (!h || !report) return BFTSIM_EINVAL;
+    if (int rc = archive_args(h, hdr, slot_bytes, hdr_len, "bftsim_archive_trace")) return rc;
+    ArchiveCont ac{};
+    ac.hdr = hdr; ac.slot_bytes = slot_bytes; ac.hdr_len = hdr_len; ac.out = out; ac.report = report;
+    bftsim_audit_report own;
+    return audit_host_stream(h, stream, stream_bytes, frame_off, frames, inst_frame0, inst_count, max_heights, key_cap,
+                             audit_out, audit_report ? audit_report : &own, &ac);
+}
+int bftsim_archive_last_trace(bftsim_t* h, uint64_t inst_begin, uint64_t inst_count, uint32_t key_cap, uint8_t* hdr,
+                              uint64_t slot_bytes, uint32_t* hdr_len, const bftsim_archive_out* out,
+                              const bftsim_audit_out* audit_out, bftsim_audit_report* audit_report,
+                              bftsim_archive_report* report) {
+    if (!h || !report) return BFTSIM_EINVAL;
+    if (int rc = archive_args(h, hdr, slot_bytes, hdr_len, "bftsim_archive_last_trace")) return rc;
+    ArchiveCont ac{};
+    ac.hdr = hdr; ac.slot_bytes = slot_bytes; ac.hdr_len = hdr_len; ac.out = out; ac.report = report;
+    bftsim_audit_report own;
+    return audit_kept_trace(h, inst_begin, inst_count, key_cap, audit_out, audit_report ? audit_report : &own, &ac);
+}
+int bftsim_archive_last_ms(bftsim_t* h, float* audit_ms, float* pick_ms, float* emit_ms, float* copy_ms) {
+    if (!h) return BFTSIM_EINVAL;
+    if (audit_ms) *audit_ms = h->archive_ms[0];
+    if (pick_ms) *pick_ms = h->archive_ms[1];
+    if (emit_ms) *emit_ms = h->archive_ms[2];
+    if (copy_ms) *copy_ms = h->archive_ms[3];
     return BFTSIM_OK;
 }
 

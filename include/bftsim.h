@@ -335,6 +335,53 @@ int bftsim_audit_last_trace(bftsim_t *h, uint64_t inst_begin, uint64_t inst_coun
  * copies (the stream to the device, the outputs back), as scripts/audit_bench.py records them */
 int bftsim_audit_last_ms(bftsim_t *h, float *decode_ms, float *recover_ms, float *tally_ms, float *copy_ms);
 
+/* the archiver (SPEC.md §11e): what a node that only listened can write down of the chain it saw. The observer's passes,
+ * then for every certified height the ledger Header assembled on the device from the bytes alone: the 12 leading fields of
+ * the block in the first accepted PrePrepare frame of that height whose digest is the certificate's, re-encoded
+ * canonically, and as votes the commit seals of the Commit frames that set the certificate's voter bits, ascending by
+ * validator, each as it was received. The output has the slot layout of bftsim_export_ledger, so bftsim_verify_ledger
+ * takes it as is. */
+#define BFTSIM_ARCHIVE_OK 0u          /* the slot holds the header */
+#define BFTSIM_ARCHIVE_NONE 1u        /* the height has no certificate: hdr_len 0 */
+#define BFTSIM_ARCHIVE_NO_PROPOSAL 2u /* certified, but the instance has no accepted PrePrepare frame with the
+                                         certificate's (height, digest): hdr_len 0 */
+struct bftsim_archive_report {
+    uint64_t headers;               /* slots written */
+    uint64_t by_status[3];
+    uint64_t votes;                 /* seals written */
+    uint64_t foreign_seals;         /* of those, taken from BFTSIM_AUDIT_SEAL_FOREIGN frames */
+    uint64_t archived_instances;    /* instances whose OK slots form a prefix and the rest are NONE */
+};
+typedef struct bftsim_archive_report bftsim_archive_report;
+struct bftsim_archive_out {         /* host, caller-owned, any pointer may be NULL; rows inst * max_heights + x - 1 */
+    uint8_t *status;                /* BFTSIM_ARCHIVE_* */
+    uint32_t *pp_frame;             /* the PrePrepare frame used (index within the instance), 0xffffffff if none */
+    uint16_t *n_votes;              /* seals in the slot (0 unless OK) */
+    uint64_t *archived_height;      /* [inst_count] the largest x with slots 1..x all OK */
+};
+typedef struct bftsim_archive_out bftsim_archive_out;
+/* stream .. key_cap, audit_out and audit_report (both nullable): as bftsim_audit_trace, whose refusals are this call's
+ * and whose outputs those two receive unchanged. hdr [inst_count * max_heights * slot_bytes] / hdr_len
+ * [inst_count * max_heights]: host buffers, slot i * max_heights + x - 1; of a slot only its first
+ * bftsim_ledger_slot_bytes(config.n) bytes are written (the header, then zeros). BFTSIM_EINVAL too for a null hdr,
+ * hdr_len or report and for slot_bytes below bftsim_ledger_slot_bytes(config.n); BFTSIM_ENOMEM for 2^31 slots or more. A
+ * refused call writes nothing; hostile frame contents are never an error; the handle's run state is untouched; no
+ * secrets are needed. A header that would not fit its slot fails the call with BFTSIM_EHIP before any copy to the host. */
+int bftsim_archive_trace(bftsim_t *h, const uint8_t *stream, uint64_t stream_bytes, const uint64_t *frame_off, uint64_t frames,
+                         const uint64_t *inst_frame0, uint64_t inst_count, uint32_t max_heights, uint32_t key_cap,
+                         uint8_t *hdr, uint64_t slot_bytes, uint32_t *hdr_len, const bftsim_archive_out *out,
+                         const bftsim_audit_out *audit_out, bftsim_audit_report *audit_report,
+                         bftsim_archive_report *report);
+/* the same over the kept trace of the last launch, as bftsim_audit_last_trace: the stream never leaves the device */
+int bftsim_archive_last_trace(bftsim_t *h, uint64_t inst_begin, uint64_t inst_count, uint32_t key_cap, uint8_t *hdr,
+                              uint64_t slot_bytes, uint32_t *hdr_len, const bftsim_archive_out *out,
+                              const bftsim_audit_out *audit_out, bftsim_audit_report *audit_report,
+                              bftsim_archive_report *report);
+/* diagnostics: device times (ms, HIP events) of the last archive call: the observer's passes (decode, recoveries,
+ * classification + tally), the pick kernel, the emit and heights kernels, and the copies, as scripts/archive_bench.py
+ * records them */
+int bftsim_archive_last_ms(bftsim_t *h, float *audit_ms, float *pick_ms, float *emit_ms, float *copy_ms);
+
 /* the importer (SPEC.md §11d): what a syncing node runs on every Header it is handed, Engine::verify_header with
  * seal = true and verify_seal (src/consensus/backend.rs:319-367), batched: every header of every instance's ledger,
  * verified from untrusted bytes on the device.
