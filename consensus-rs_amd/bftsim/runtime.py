@@ -68,6 +68,9 @@ def lib():
                                           ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
                                           ctypes.c_void_p]
         L.bftsim_trace_last_ms.argtypes = [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_float)] * 3
+        L.bftsim_set_trace_twins.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        L.bftsim_trace_twin_counts.argtypes = [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_uint64)] * 2
+        L.bftsim_trace_twins_last_ms.argtypes = [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_float)] * 3
         L.bftsim_audit_trace.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
                                          ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32,
                                          ctypes.c_uint32, ctypes.POINTER(_abi.CAuditOut),
@@ -332,6 +335,24 @@ class Simulator:
     def set_trace_keep(self, on: bool):
         """crypto_verify keeps on the device what export_trace needs, until the next launch (bftsim_set_trace_keep)."""
         _check(self.h, lib().bftsim_set_trace_keep(self.h, 1 if on else 0), "bftsim_set_trace_keep")
+
+    def set_trace_twins(self, on):
+        """The next keeping crypto_verify adds every equivocating broadcast's second frame to the trace
+        (bftsim_set_trace_twins, SPEC.md §11f); on: a bool, or 0 / 1 (anything else is refused)."""
+        _check(self.h, lib().bftsim_set_trace_twins(self.h, int(on)), "bftsim_set_trace_twins")
+
+    def trace_twin_counts(self):
+        """(PrePrepare twins, vote twins) of the last kept trace (bftsim_trace_twin_counts)."""
+        a, b = ctypes.c_uint64(), ctypes.c_uint64()
+        _check(self.h, lib().bftsim_trace_twin_counts(self.h, ctypes.byref(a), ctypes.byref(b)), "bftsim_trace_twin_counts")
+        return a.value, b.value
+
+    def trace_twins_ms(self):
+        """(mark + scan + merge, digests, signing) of the last verify's twin passes, device ms."""
+        a, b, c = ctypes.c_float(), ctypes.c_float(), ctypes.c_float()
+        _check(self.h, lib().bftsim_trace_twins_last_ms(self.h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)),
+               "bftsim_trace_twins_last_ms")
+        return a.value, b.value, c.value
 
     def trace_sizes(self):
         """(frames [n] u32, stream bytes [n] u64) per instance of the last launch's trace (after crypto_verify)."""

@@ -7,6 +7,7 @@ import numpy as np
 
 MT_PREPREPARE, MT_PREPARE, MT_COMMIT, MT_ROUND_CHANGE = 1, 2, 3, 4
 FLAG_FORGED, FLAG_WILD, FLAG_EQUIV, FLAG_OLD = 1, 2, 4, 8
+FLAG_TWIN = 1 << 16       # the frame is a twin (Simulator.set_trace_twins, SPEC.md §11f): not a log entry's own frame
 
 
 class Trace:
@@ -26,6 +27,7 @@ class Trace:
     sender = property(lambda self: self.meta[:, 1] >> 16)
     flags = property(lambda self: self.meta[:, 2])
     instance = property(lambda self: self.meta[:, 3])
+    twin = property(lambda self: (self.meta[:, 2] & FLAG_TWIN) != 0)
 
     def frame(self, k: int) -> bytes:
         return bytes(self.stream[int(self.frame_off[k]):int(self.frame_off[k + 1])])

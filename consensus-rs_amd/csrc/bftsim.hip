@@ -29,6 +29,7 @@
 #include "bft_fast64.h"
 #include "bft_crypto.h"
 #include "bft_trace.h"
+#include "bft_twins.h"
 #include "bft_audit.h"
 #include "bft_archive.h"
 #include "bft_ledger.h"
@@ -125,40 +126,7 @@ struct CryptoArgs {
     unsigned long long* counts;       // [8] messages, commits, forged, recovered-as-sender, mismatches, seal errors
 };
 
-// parent hash of the block at height x as the run left it: the canonical row x-1 (genesis at 1); a
-// height above the committed chain + 1 has no known parent and uses 0^32 (SPEC.md §11)
-__device__ inline void crypto_parent(const Params& p, uint32_t il, uint32_t x, uint32_t prev[8]) {
-    const uint32_t ch = p.committed_height[il];
-    if (x <= 1) {
-        for (int i = 0; i < 8; ++i)
-            prev[i] = (uint32_t)p.genesis_hash[4 * i] | ((uint32_t)p.genesis_hash[4 * i + 1] << 8) |
-                      ((uint32_t)p.genesis_hash[4 * i + 2] << 16) | ((uint32_t)p.genesis_hash[4 * i + 3] << 24);
-    } else if (x - 1 <= ch) {
-        const uint32_t* ph = (const uint32_t*)(p.hash + ((uint64_t)il * p.rows + (x - 1)) * 32);
-        for (int i = 0; i < 8; ++i) prev[i] = ph[i];
-    } else {
-        for (int i = 0; i < 8; ++i) prev[i] = 0;
-    }
-}
-// Subject digest of a logged block id: the canonical row's hash when the block is the committed one
-// at its height, else the hash of its header over crypto_parent
-__device__ inline void crypto_block_digest(const Params& p, uint32_t il, uint64_t b, uint8_t* hbuf, uint8_t out[32]) {
-    const uint32_t x = blk_h(b), prop = blk_prop(b), var = blk_var(b);
-    if (!blk_valid(b) || x == 0) { for (int i = 0; i < 32; ++i) out[i] = 0; return; }
-    if (x <= p.committed_height[il]) {
-        const uint32_t* row = p.rec + ((uint64_t)il * p.rows + x) * 4;
-        if ((row[1] & 0xffffu) == prop && ((row[1] >> 16) & 1u) == var) {
-            const uint8_t* hs = p.hash + ((uint64_t)il * p.rows + x) * 32;
-            for (int i = 0; i < 32; ++i) out[i] = hs[i];
-            return;
-        }
-    }
-    uint32_t prev[8], w[8];
-    crypto_parent(p, il, x, prev);
-    const uint64_t time = p.genesis_time + (uint64_t)p.block_period * ((uint64_t)blk_T(b) + 1ull);
-    lane_block_hash(hbuf, prev, p.addresses + 20u * prop, p.seed, p.first_instance + il, x, prop, var, time, w);
-    for (int i = 0; i < 32; ++i) out[i] = (uint8_t)(w[i >> 2] >> (8 * (i & 3)));
-}
+// crypto_parent / crypto_block_digest (the digest of a logged block id as the run left it): bft_twins.h
 
 // pass 1 (workgroup per instance): digests, signing keys, the commits' seal digests
 __global__ __launch_bounds__(64) void bft_crypto_prep_kernel(Params p, CryptoArgs a) {
@@ -355,8 +323,40 @@ struct TraceArgs {
     const uint8_t* sigs;
     const uint8_t* seals;
 };
-// the frame inputs of dense message m; hbuf: this lane's LANE_HASH_BUF bytes (a Preprepare's header)
-__device__ inline trace::Msg trace_msg(const Params& p, const TraceArgs& a, uint64_t m, uint8_t* hbuf) {
+// twins (bftsim_set_trace_twins, SPEC.md §11f): the merged frame index and, per twin slot, what TraceArgs' dense arrays
+// hold per message. An argument of the twin kernels alone (TwinOpt)
+struct TwinArgs {
+    const uint64_t* fmap;             // [frames] message, | twins::F_TWIN for a twin
+    const uint32_t* tslot;            // [messages + 1] twins before message m: a twin's slot
+    const uint8_t* traw;
+    const uint32_t* tmsg_k;
+    const uint8_t* tsigs;
+    const uint8_t* tseals;
+};
+// the last argument of a trace kernel: nothing for a trace without twins, whose kernels so keep their arguments
+template <bool TW> struct TwinOpt {};
+template <> struct TwinOpt<true> { TwinArgs a; };
+template <bool TW>
+__device__ inline const TwinArgs* twin_args(const TwinOpt<TW>& t) {
+    if constexpr (TW) return &t.a; else return nullptr;
+}
+// frame f of the trace -> its dense message; TW (twins on): through the merged index, tw = the frame is the twin
+template <bool TW>
+__device__ inline uint64_t trace_frame_msg(const TwinArgs* t, uint64_t f, bool& tw) {
+    if constexpr (TW) {
+        const uint64_t v = t->fmap[f];
+        tw = (v & twins::F_TWIN) != 0;
+        return v & ~twins::F_TWIN;
+    } else {
+        tw = false;
+        return f;
+    }
+}
+// the frame inputs of dense message m, or of its twin (tw): the same message for the other variant of its block, from
+// the twin slot's arrays; hbuf: this lane's LANE_HASH_BUF bytes (a Preprepare's header)
+template <bool TW>
+__device__ inline trace::Msg trace_msg(const Params& p, const TraceArgs& a, const TwinArgs* ta, uint64_t m, bool tw,
+                                       uint8_t* hbuf) {
     const uint64_t ref = a.mref[m];
     const uint32_t il = (uint32_t)(ref / a.cap);
     const uint32_t* e = a.mlog + ref * MLOG_WORDS;
@@ -370,8 +370,16 @@ __device__ inline trace::Msg trace_msg(const Params& p, const TraceArgs& a, uint
     g.hlen = 0;
     g.sig = a.sigs + m * 65;
     g.seal = g.code == MT_COMMIT ? a.seals + (uint64_t)a.msg_k[m] * 65 : nullptr;
+    if constexpr (TW) {
+        if (tw) {
+            const uint64_t t = ta->tslot[m];
+            g.digest = ta->traw + t * 32;
+            g.sig = ta->tsigs + t * 65;
+            g.seal = g.code == MT_COMMIT ? ta->tseals + (uint64_t)ta->tmsg_k[t] * 65 : nullptr;
+        }
+    }
     if (g.code == MT_PREPREPARE) {
-        const uint64_t b = (uint64_t)e[4] | ((uint64_t)e[5] << 32);
+        const uint64_t b = ((uint64_t)e[4] | ((uint64_t)e[5] << 32)) ^ (TW && tw ? twins::BLK_FLIP : 0ull);
         const uint32_t x = blk_h(b), prop = blk_prop(b), var = blk_var(b);
         uint32_t prev[8];
         crypto_parent(p, il, x, prev);
@@ -382,29 +390,39 @@ __device__ inline trace::Msg trace_msg(const Params& p, const TraceArgs& a, uint
     }
     return g;
 }
-// size pass: lens[m] = the frame's length, lens[M] = 0 (the scan's last entry is the total)
-__global__ __launch_bounds__(64) void bft_trace_size_kernel(Params p, TraceArgs a, uint64_t M, uint64_t* lens) {
+// size pass: lens[f] = the frame's length, lens[F] = 0 (the scan's last entry is the total)
+template <bool TW>
+__global__ __launch_bounds__(64) void bft_trace_size_kernel(Params p, TraceArgs a, uint64_t F, uint64_t* lens, TwinOpt<TW> to) {
+    const TwinArgs* t = twin_args(to);
     __shared__ __attribute__((aligned(16))) uint8_t hb[64 * LANE_HASH_BUF];
-    const uint64_t m = (uint64_t)blockIdx.x * 64u + threadIdx.x;
-    if (m >= M) { if (m == M) lens[M] = 0; return; }
-    lens[m] = trace::frame_len(trace_msg(p, a, m, hb + threadIdx.x * LANE_HASH_BUF));
+    const uint64_t f = (uint64_t)blockIdx.x * 64u + threadIdx.x;
+    if (f >= F) { if (f == F) lens[F] = 0; return; }
+    bool tw;
+    const uint64_t m = trace_frame_msg<TW>(t, f, tw);
+    lens[f] = trace::frame_len(trace_msg<TW>(p, a, t, m, tw, hb + threadIdx.x * LANE_HASH_BUF));
 }
-// first byte of each instance: ioff[i] = foff[moff[i]], i <= n_inst
-__global__ __launch_bounds__(256) void bft_trace_inst_kernel(const uint64_t* moff, const uint64_t* foff, uint64_t n1,
+
+// first byte of each instance: ioff[i] = foff[if0[i]], i <= n_inst (if0: the instances' first frames)
+__global__ __launch_bounds__(256) void bft_trace_inst_kernel(const uint64_t* if0, const uint64_t* foff, uint64_t n1,
                                                              uint64_t* ioff) {
     const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-    if (i < n1) ioff[i] = foff[moff[i]];
+    if (i < n1) ioff[i] = foff[if0[i]];
 }
-// {tick, phase | code << 8 | sender << 16, flags, instance - inst_begin} of messages [m0, m1)
-__global__ __launch_bounds__(256) void bft_trace_meta_kernel(TraceArgs a, uint64_t m0, uint64_t m1, uint32_t inst_begin,
-                                                             uint32_t* meta) {
-    const uint64_t m = m0 + (uint64_t)blockIdx.x * 256u + threadIdx.x;
-    if (m >= m1) return;
-    const uint64_t ref = a.mref[m];
+// {tick, phase | code << 8 | sender << 16, flags, instance - inst_begin} of frames [f0, f1); a twin's flags carry
+// twins::META_TWIN
+template <bool TW>
+__global__ __launch_bounds__(256) void bft_trace_meta_kernel(TraceArgs a, uint64_t f0, uint64_t f1, uint32_t inst_begin,
+                                                             uint32_t* meta, TwinOpt<TW> to) {
+    const TwinArgs* t = twin_args(to);
+    const uint64_t f = f0 + (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (f >= f1) return;
+    bool tw;
+    const uint64_t ref = a.mref[trace_frame_msg<TW>(t, f, tw)];
     const uint32_t* e = a.mlog + ref * MLOG_WORDS;
-    ((uint4*)meta)[m - m0] = make_uint4(e[0], e[1], e[6], (uint32_t)(ref / a.cap) - inst_begin);
+    ((uint4*)meta)[f - f0] = make_uint4(e[0], e[1], e[6] | (tw ? twins::META_TWIN : 0u), (uint32_t)(ref / a.cap) - inst_begin);
 }
-// emit pass (`out` holds the frames of [m0, m1)): a wave per 64 consecutive frames, which are one contiguous piece
+
+// emit pass (`out` holds the frames of [f0, f1)): a wave per 64 consecutive frames, which are one contiguous piece
 // of the stream. Each lane expands
 // its frame into an LDS stage laid out like that piece (as many whole frames per round as the stage holds), then
 // the wave copies the stage out with coalesced 16-byte stores (byte stores for the unaligned head and tail).
@@ -412,16 +430,20 @@ __global__ __launch_bounds__(256) void bft_trace_meta_kernel(TraceArgs a, uint64
 // round's frames, so a disagreement of the two passes only counts in *err. Only a Preprepare needs a header
 // buffer: a round takes at most TRACE_PP of them, which keeps the block at 4 per CU.
 constexpr uint32_t TRACE_STAGE = 32 * 1024, TRACE_PP = 16;
-__global__ __launch_bounds__(64) void bft_trace_emit_kernel(Params p, TraceArgs a, uint64_t m0, uint64_t m1,
-                                                            const uint64_t* foff, uint8_t* out, uint32_t* err) {
+template <bool TW>
+__global__ __launch_bounds__(64) void bft_trace_emit_kernel(Params p, TraceArgs a, uint64_t f0, uint64_t f1,
+                                                            const uint64_t* foff, uint8_t* out, uint32_t* err, TwinOpt<TW> to) {
+    const TwinArgs* t = twin_args(to);
     __shared__ __attribute__((aligned(16))) uint8_t hb[TRACE_PP * LANE_HASH_BUF];
     __shared__ __attribute__((aligned(16))) uint8_t stage[TRACE_STAGE];
     const uint32_t lane = threadIdx.x;
-    const uint64_t mb = m0 + (uint64_t)blockIdx.x * 64u;
-    const uint32_t live = (uint32_t)(m1 - mb < 64u ? m1 - mb : 64u);
-    const uint64_t m = mb + (lane < live ? lane : live);        // idle lanes: the empty frame at the block's end
-    const uint64_t base = foff[m0];
-    const uint64_t o0 = foff[m] - base, o1 = foff[lane < live ? m + 1 : m] - base;
+    const uint64_t fb = f0 + (uint64_t)blockIdx.x * 64u;
+    const uint32_t live = (uint32_t)(f1 - fb < 64u ? f1 - fb : 64u);
+    const uint64_t f = fb + (lane < live ? lane : live);        // idle lanes: the empty frame at the block's end
+    const uint64_t base = foff[f0];
+    const uint64_t o0 = foff[f] - base, o1 = foff[lane < live ? f + 1 : f] - base;
+    bool tw = false;
+    const uint64_t m = TW ? (lane < live ? trace_frame_msg<TW>(t, f, tw) : 0) : f;
     const bool pp = lane < live && ((a.mlog[a.mref[m] * MLOG_WORDS + 1] >> 8) & 0xffu) == (uint32_t)MT_PREPREPARE;
     const uint64_t ppmask = __ballot(pp);
     uint32_t first = 0;
@@ -440,7 +462,7 @@ __global__ __launch_bounds__(64) void bft_trace_emit_kernel(Params p, TraceArgs 
         if (fits && lane < live) {
             const uint32_t len = (uint32_t)(o1 - o0);
             if (trace::write_frame(stage + shift + (uint32_t)(o0 - r0), len,
-                                   trace_msg(p, a, m, hb + (pp ? slot : 0u) * LANE_HASH_BUF)) != len)
+                                   trace_msg<TW>(p, a, t, m, tw, hb + (pp ? slot : 0u) * LANE_HASH_BUF)) != len)
                 atomicAdd(err, 1u);
         }
         __syncthreads();
@@ -530,10 +552,19 @@ struct bftsim {
     bool trace_keep = false;
     uint8_t* d_tkeep = nullptr;       // one allocation: moff, mref, raw, msg_k, sigs, seals (trace_args points into it)
     bft::TraceArgs trace_args{};
+    bft::TwinArgs twin_args{};
     uint64_t trace_n = 0, trace_M = 0;    // instances (0: nothing kept) and messages it holds
     uint64_t* d_tfoff = nullptr;      // [M + 1] frame offsets, then [n + 1] instance offsets, then the error counter
-    std::vector<uint64_t> trace_moff, trace_ioff;   // host, [n + 1]: first message / first stream byte of each instance
+    std::vector<uint64_t> trace_moff, trace_ioff;   // host, [n + 1]: first frame / first stream byte of each instance
     float trace_ms[3] = {0, 0, 0};    // size pass + scan, emit kernel, device-to-host copies of the last calls
+    // twins (bftsim_set_trace_twins, SPEC.md §11f): the kept trace's frames are its messages and their twins
+    bool trace_twins = false;         // what the next keeping verify does
+    bool trace_has_twins = false;     // the kept trace was built with twins on
+    uint8_t* d_twkeep = nullptr;      // one allocation: tslot, if0, fmap, traw, tmsg_k, tsigs, tseals (trace_args points into it)
+    const uint64_t* d_tif0 = nullptr; // [n + 1] first frame of each instance (twins off: trace_args.moff)
+    uint64_t trace_F = 0;             // frames: trace_M + the twins
+    uint64_t twin_counts[2] = {0, 0}; // PrePrepare twins, vote twins of the kept trace
+    float twin_ms[3] = {0, 0, 0};     // mark + scan + merge, digests, signing of the last verify with twins on
     float audit_ms[4] = {0, 0, 0, 0}; // decode, recoveries, classify + tally, copies of the last audit (SPEC.md §11c)
     float ledger_ms[4] = {0, 0, 0, 0};// decode, recoveries, tally + link, copies of the last bftsim_verify_ledger (§11d)
     uint8_t* d_tips = nullptr;        // [cap_inst * 32]
@@ -671,7 +702,7 @@ struct DevMem {                       // a device allocation
     template <class T> T* release() { T* r = (T*)p; p = nullptr; return r; }   // the handle takes the allocation over
 };
 struct Events {                       // up to MAX timing events
-    static constexpr int MAX = 5;
+    static constexpr int MAX = 6;
     hipEvent_t ev[MAX] = {};
     Events() = default;
     Events(const Events&) = delete;
@@ -706,9 +737,11 @@ static void use_set0_scratch(bftsim* h) {
 
 static void trace_drop(bftsim* h) {
     if (!h->d_tkeep && !h->d_tfoff && h->trace_n == 0) return;   // the launch path: nothing kept, no HIP call
-    (void)hipFree(h->d_tkeep); (void)hipFree(h->d_tfoff);
-    h->d_tkeep = nullptr; h->d_tfoff = nullptr;
-    h->trace_n = h->trace_M = 0;
+    (void)hipFree(h->d_tkeep); (void)hipFree(h->d_tfoff); (void)hipFree(h->d_twkeep);
+    h->d_tkeep = nullptr; h->d_tfoff = nullptr; h->d_twkeep = nullptr; h->d_tif0 = nullptr;
+    h->trace_n = h->trace_M = h->trace_F = 0;
+    h->trace_has_twins = false;
+    h->twin_counts[0] = h->twin_counts[1] = 0;
     h->trace_moff.clear(); h->trace_ioff.clear();
 }
 
@@ -1802,6 +1835,109 @@ int bftsim_set_crypto(bftsim_t* h, const uint8_t* secrets32, const uint8_t* forg
     return BFTSIM_OK;
 }
 
+}  // extern "C"
+
+// The twins of the trace a verify is keeping (bftsim_set_trace_twins, SPEC.md §11f), on the verify's
+// stream and in buffers of their own: the pass's arrays `a` are read, never written. tk: what the handle takes over
+// (the merged index and the twins' digests, signatures and seals); ta: what the trace's twin kernels read.
+namespace {
+struct TwinKeep {
+    DevMem keep;
+    const uint64_t* if0 = nullptr;
+    std::vector<uint64_t> if0_host;
+    uint64_t T = 0, counts[2] = {0, 0};
+};
+}  // namespace
+static int twins_build(bftsim* h, const bft::Params& p, const bft::CryptoArgs& a, uint64_t n, uint64_t M, hipStream_t s,
+                       TwinKeep& tk, bft::TwinArgs& ta) {
+    namespace tw = bft::twins;
+    SigApi& sa = sig_api();
+    if (M + 1 > 0x7fffffffull) return fail(h, BFTSIM_EINVAL, "trace twins: too many messages for one scan");
+    auto up = [](uint64_t b) { return (b + 15) & ~15ull; };
+    DevMem idx, tmp, work;
+    Events ev;
+    HIPCHECK(h, ev.create(6));
+    HIPCHECK(h, idx.alloc(up(n * 32) + 2 * up((M + 1) * 4) + 16));
+    tw::Args t{};
+    t.mlog = a.mlog; t.cap = a.cap; t.n_val = a.n_val; t.seed = p.seed; t.first_instance = p.first_instance;
+    t.byz_count = p.byz_count; t.n_inst = n; t.M = M; t.moff = a.moff; t.mref = a.mref; t.key = a.key;
+    uint8_t* q = idx.as<uint8_t>();
+    t.byz = (uint64_t*)q; q += up(n * 32);
+    t.mark = (uint32_t*)q; q += up((M + 1) * 4);
+    uint32_t* scan = (uint32_t*)q; q += up((M + 1) * 4);
+    t.counts = (unsigned long long*)q;
+    size_t tb = 0;
+    HIPCHECK(h, hipcub::DeviceScan::ExclusiveSum(nullptr, tb, t.mark, scan, (int)(M + 1)));
+    HIPCHECK(h, tmp.alloc(tb ? tb : 16));
+    HIPCHECK(h, hipMemsetAsync(t.counts, 0, 8, s));
+    HIPCHECK(h, hipEventRecord(ev[0], s));
+    HIPCHECK(h, tw::launch_mark(t, s));
+    HIPCHECK(h, hipcub::DeviceScan::ExclusiveSum(tmp.p, tb, t.mark, scan, (int)(M + 1), s));
+    uint32_t T32 = 0;
+    unsigned long long packed = 0;
+    HIPCHECK(h, hipMemcpyAsync(&T32, scan + M, 4, hipMemcpyDeviceToHost, s));
+    HIPCHECK(h, hipMemcpyAsync(&packed, t.counts, 8, hipMemcpyDeviceToHost, s));
+    HIPCHECK(h, hipStreamSynchronize(s));
+    const uint64_t T = T32, Tx = T ? T : 1;
+    tk.counts[0] = packed & 0xffffffffull;
+    tk.counts[1] = packed >> 32;
+    if (tk.counts[0] + tk.counts[1] != T) return fail(h, BFTSIM_EHIP, "trace twins: the marks' counts and their scan disagree");
+    // kept: tslot, if0, fmap, tmsg, traw, tmsg_k, tsigs, tseals; temporary: the twins' keys and digests
+    HIPCHECK(h, tk.keep.alloc(up((M + 1) * 4) + up((n + 1) * 8) + up((M + T) * 8) + up(Tx * 8) + up(Tx * 32) + up(Tx * 4) +
+                              2 * up(Tx * 65)));
+    HIPCHECK(h, work.alloc(2 * up(Tx * 4) + 2 * up(Tx * 32) + up(Tx) + 16));
+    q = tk.keep.as<uint8_t>();
+    t.tslot = (uint32_t*)q; q += up((M + 1) * 4);
+    t.if0 = (uint64_t*)q; q += up((n + 1) * 8);
+    t.fmap = (uint64_t*)q; q += up((M + T) * 8);
+    t.tmsg = (uint64_t*)q; q += up(Tx * 8);
+    t.raw = q; q += up(Tx * 32);
+    t.msg_k = (uint32_t*)q; q += up(Tx * 4);
+    uint8_t* tsigs = q; q += up(Tx * 65);
+    uint8_t* tseals = q;
+    q = work.as<uint8_t>();
+    t.tkey = (uint32_t*)q; q += up(Tx * 4);
+    t.seal_key = (uint32_t*)q; q += up(Tx * 4);
+    t.sign_dig = q; q += up(Tx * 32);
+    t.seal_dig = q; q += up(Tx * 32);
+    uint8_t* ok = q; q += up(Tx);
+    t.ncm = (uint32_t*)q;
+    t.seals = tseals;
+    t.T = T;
+    HIPCHECK(h, hipMemcpyAsync(t.tslot, scan, (M + 1) * 4, hipMemcpyDeviceToDevice, s));
+    HIPCHECK(h, hipMemsetAsync(t.ncm, 0, 4, s));
+    HIPCHECK(h, tw::launch_merge(t, s));
+    HIPCHECK(h, hipEventRecord(ev[1], s));
+    HIPCHECK(h, tw::launch_prep(p, t, s));
+    HIPCHECK(h, hipEventRecord(ev[2], s));
+    uint32_t ncm = 0;
+    tk.if0_host.resize(n + 1);
+    HIPCHECK(h, hipMemcpyAsync(&ncm, t.ncm, 4, hipMemcpyDeviceToHost, s));
+    HIPCHECK(h, hipMemcpyAsync(tk.if0_host.data(), t.if0, (n + 1) * 8, hipMemcpyDeviceToHost, s));
+    HIPCHECK(h, hipStreamSynchronize(s));
+    if (ncm > T) return fail(h, BFTSIM_EHIP, "trace twins: more Commit twins than twins");
+    // commit seals first: they are part of the Commit's sign payload
+    if (ncm && sa.sign(h->sig, h->d_keys, t.seal_key, t.seal_dig, ncm, tseals, ok, s) != 0)
+        return fail(h, BFTSIM_EHIP, std::string("bftsig_sign (twin seals): ") + sa.last_error(h->sig));
+    HIPCHECK(h, hipEventRecord(ev[3], s));
+    HIPCHECK(h, tw::launch_digest(p, t, s));
+    HIPCHECK(h, hipEventRecord(ev[4], s));
+    if (T && sa.sign(h->sig, h->d_keys, t.tkey, t.sign_dig, T, tsigs, ok, s) != 0)
+        return fail(h, BFTSIM_EHIP, std::string("bftsig_sign (twins): ") + sa.last_error(h->sig));
+    HIPCHECK(h, hipEventRecord(ev[5], s));
+    HIPCHECK(h, hipStreamSynchronize(s));
+    float ms[5];
+    for (int k = 0; k < 5; ++k) HIPCHECK(h, hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]));
+    h->twin_ms[0] = ms[0];
+    h->twin_ms[1] = ms[1] + ms[3];
+    h->twin_ms[2] = ms[2] + ms[4];
+    tk.T = T;
+    tk.if0 = t.if0;
+    ta.fmap = t.fmap; ta.tslot = t.tslot; ta.traw = t.raw; ta.tmsg_k = t.msg_k; ta.tsigs = tsigs; ta.tseals = tseals;
+    return BFTSIM_OK;
+}
+
+extern "C" {
 int bftsim_crypto_verify(bftsim_t* h, bftsim_crypto_report* out, uint64_t capacity, uint8_t* inst_checksum,
                          uint32_t* inst_messages) {
     if (!h || !out) return BFTSIM_EINVAL;
@@ -1896,6 +2032,11 @@ int bftsim_crypto_verify(bftsim_t* h, bftsim_crypto_report* out, uint64_t capaci
         HIPCHECK(h, hipGetLastError());
         h->vsig_n = n;
     }
+    bft::TwinArgs ta{};
+    TwinKeep tk;
+    const bool twins = keep && h->trace_twins && M;
+    if (twins)
+        if (int rc = twins_build(h, p, a, n, M, s, tk, ta)) return rc;
     unsigned long long c[8] = {0};
     HIPCHECK(h, hipMemcpyAsync(c, a.counts, 64, hipMemcpyDeviceToHost, s));
     if (inst_checksum) HIPCHECK(h, hipMemcpyAsync(inst_checksum, a.inst_ck, n * 32, hipMemcpyDeviceToHost, s));
@@ -1903,9 +2044,20 @@ int bftsim_crypto_verify(bftsim_t* h, bftsim_crypto_report* out, uint64_t capaci
     if (keep) {
         h->d_tkeep = kpool.release<uint8_t>();
         h->trace_args = bft::TraceArgs{h->d_mlog, h->mlog_cap, a.moff, a.mref, a.raw, a.msg_k, a.sigs, a.seals};
+        h->twin_args = ta;
         h->trace_n = n;
         h->trace_M = M;
+        h->trace_F = M + tk.T;
         h->trace_moff = off;
+        h->d_tif0 = a.moff;
+        if (twins) {
+            h->d_twkeep = tk.keep.release<uint8_t>();
+            h->trace_has_twins = true;
+            h->trace_moff.swap(tk.if0_host);
+            h->d_tif0 = tk.if0;
+            h->twin_counts[0] = tk.counts[0];
+            h->twin_counts[1] = tk.counts[1];
+        }
     }
     out->messages = c[0];
     out->seals = c[1];
@@ -1963,7 +2115,7 @@ static int trace_ready(bftsim* h, const char* what) {
 // size pass + scan over every kept message, once per verify: d_tfoff and the host's per-instance offsets
 static int trace_size_pass(bftsim* h) {
     if (h->d_tfoff) return BFTSIM_OK;
-    const uint64_t n = h->trace_n, M = h->trace_M;
+    const uint64_t n = h->trace_n, M = h->trace_F;               // every frame: the messages and their twins
     if (M + 1 > 0x7fffffffull) return fail(h, BFTSIM_EINVAL, "trace: too many messages for one scan");
     HIPCHECK(h, hipSetDevice(h->device));
     hipStream_t s = h->last_stream;
@@ -1979,12 +2131,16 @@ static int trace_size_pass(bftsim* h) {
     std::vector<uint64_t> ioff(n + 1);
     bft::Params p = make_params(h, h->last_first, n);
     HIPCHECK(h, hipEventRecord(ev[0], s));
-    hipLaunchKernelGGL(bft::bft_trace_size_kernel, dim3((uint32_t)((M + 1 + 63) / 64)), dim3(64), 0, s, p,
-                       h->trace_args, M, lens);
+    if (h->trace_has_twins)
+        hipLaunchKernelGGL(bft::bft_trace_size_kernel<true>, dim3((uint32_t)((M + 1 + 63) / 64)), dim3(64), 0, s, p,
+                           h->trace_args, M, lens, bft::TwinOpt<true>{h->twin_args});
+    else
+        hipLaunchKernelGGL(bft::bft_trace_size_kernel<false>, dim3((uint32_t)((M + 1 + 63) / 64)), dim3(64), 0, s, p,
+                           h->trace_args, M, lens, bft::TwinOpt<false>{});
     HIPCHECK(h, hipGetLastError());
     HIPCHECK(h, hipcub::DeviceScan::ExclusiveSum(tmp.p, tb, lens, d, (int)(M + 1), s));
     hipLaunchKernelGGL(bft::bft_trace_inst_kernel, dim3((uint32_t)((n + 1 + 255) / 256)), dim3(256), 0, s,
-                       h->trace_args.moff, d, n + 1, d + M + 1);
+                       h->d_tif0, d, n + 1, d + M + 1);
     HIPCHECK(h, hipGetLastError());
     HIPCHECK(h, hipEventRecord(ev[1], s));
     HIPCHECK(h, hipMemcpyAsync(ioff.data(), d + M + 1, (n + 1) * 8, hipMemcpyDeviceToHost, s));
@@ -1995,19 +2151,23 @@ static int trace_size_pass(bftsim* h) {
     return BFTSIM_OK;
 }
 
-// emit pass: the frames of messages [m0, m1) into d_out, complete when it returns. The two passes must agree on
+// emit pass: frames [m0, m1) of the kept trace (messages, and their twins where it has them) into d_out, complete when it returns. The two passes must agree on
 // every frame's length; `what` names the caller in the error. t0 / t1 (or null): recorded around the kernel alone.
 static int trace_emit(bftsim* h, const char* what, uint64_t m0, uint64_t m1, uint8_t* d_out, hipEvent_t t0,
                       hipEvent_t t1) {
     hipStream_t s = h->last_stream;
-    uint32_t* d_err = (uint32_t*)(h->d_tfoff + h->trace_M + 1 + h->trace_n + 1);
+    uint32_t* d_err = (uint32_t*)(h->d_tfoff + h->trace_F + 1 + h->trace_n + 1);
     uint32_t err = 0;
     HIPCHECK(h, hipMemsetAsync(d_err, 0, 4, s));
     if (t0) HIPCHECK(h, hipEventRecord(t0, s));
     if (m1 > m0) {
         bft::Params p = make_params(h, h->last_first, h->trace_n);
-        hipLaunchKernelGGL(bft::bft_trace_emit_kernel, dim3((uint32_t)((m1 - m0 + 63) / 64)), dim3(64), 0, s, p,
-                           h->trace_args, m0, m1, h->d_tfoff, d_out, d_err);
+        if (h->trace_has_twins)
+            hipLaunchKernelGGL(bft::bft_trace_emit_kernel<true>, dim3((uint32_t)((m1 - m0 + 63) / 64)), dim3(64), 0, s, p,
+                               h->trace_args, m0, m1, h->d_tfoff, d_out, d_err, bft::TwinOpt<true>{h->twin_args});
+        else
+            hipLaunchKernelGGL(bft::bft_trace_emit_kernel<false>, dim3((uint32_t)((m1 - m0 + 63) / 64)), dim3(64), 0, s, p,
+                               h->trace_args, m0, m1, h->d_tfoff, d_out, d_err, bft::TwinOpt<false>{});
         HIPCHECK(h, hipGetLastError());
     }
     if (t1) HIPCHECK(h, hipEventRecord(t1, s));
@@ -2057,8 +2217,13 @@ int bftsim_export_trace(bftsim_t* h, uint64_t inst_begin, uint64_t inst_count, u
     if (frame_meta && frames) HIPCHECK(h, d_meta.alloc(frames * 16));
     HIPCHECK(h, ev.create(4));
     if (d_meta.p) {
-        hipLaunchKernelGGL(bft::bft_trace_meta_kernel, dim3((uint32_t)((frames + 255) / 256)), dim3(256), 0, s,
-                           h->trace_args, m0, m1, (uint32_t)inst_begin, d_meta.as<uint32_t>());
+        if (h->trace_has_twins)
+            hipLaunchKernelGGL(bft::bft_trace_meta_kernel<true>, dim3((uint32_t)((frames + 255) / 256)), dim3(256), 0, s,
+                               h->trace_args, m0, m1, (uint32_t)inst_begin, d_meta.as<uint32_t>(),
+                               bft::TwinOpt<true>{h->twin_args});
+        else
+            hipLaunchKernelGGL(bft::bft_trace_meta_kernel<false>, dim3((uint32_t)((frames + 255) / 256)), dim3(256), 0, s,
+                               h->trace_args, m0, m1, (uint32_t)inst_begin, d_meta.as<uint32_t>(), bft::TwinOpt<false>{});
         HIPCHECK(h, hipGetLastError());
     }
     if (int rc = trace_emit(h, "bftsim_export_trace", m0, m1, d_out.as<uint8_t>(), ev[0], ev[1])) return rc;
@@ -2083,6 +2248,30 @@ int bftsim_trace_last_ms(bftsim_t* h, float* size_ms, float* emit_ms, float* cop
     if (size_ms) *size_ms = h->trace_ms[0];
     if (emit_ms) *emit_ms = h->trace_ms[1];
     if (copy_ms) *copy_ms = h->trace_ms[2];
+    return BFTSIM_OK;
+}
+
+// ---- twins (SPEC.md §11f)
+int bftsim_set_trace_twins(bftsim_t* h, int on) {
+    if (!h) return BFTSIM_EINVAL;
+    if (on != 0 && on != 1) return fail(h, BFTSIM_EINVAL, "bftsim_set_trace_twins: 0 or 1");
+    h->trace_twins = on == 1;                      // read by the next keeping bftsim_crypto_verify
+    return BFTSIM_OK;
+}
+
+int bftsim_trace_twin_counts(bftsim_t* h, uint64_t* pp_twins, uint64_t* vote_twins) {
+    if (!h) return BFTSIM_EINVAL;
+    if (int rc = trace_ready(h, "bftsim_trace_twin_counts")) return rc;
+    if (pp_twins) *pp_twins = h->twin_counts[0];
+    if (vote_twins) *vote_twins = h->twin_counts[1];
+    return BFTSIM_OK;
+}
+
+int bftsim_trace_twins_last_ms(bftsim_t* h, float* index_ms, float* digest_ms, float* sign_ms) {
+    if (!h) return BFTSIM_EINVAL;
+    if (index_ms) *index_ms = h->twin_ms[0];
+    if (digest_ms) *digest_ms = h->twin_ms[1];
+    if (sign_ms) *sign_ms = h->twin_ms[2];
     return BFTSIM_OK;
 }
 

@@ -273,6 +273,27 @@ int bftsim_export_trace(bftsim_t *h, uint64_t inst_begin, uint64_t inst_count, u
  * emit kernel and device-to-host copies, as scripts/trace_bench.py records them */
 int bftsim_trace_last_ms(bftsim_t *h, float *size_ms, float *emit_ms, float *copy_ms);
 
+/* Twins (SPEC.md §11f): an equivocator's second frames. A Byzantine validator sends variant 0 of its block to some
+ * receivers and variant 1 to the others, and its votes count for both variants; the log, and so the trace, holds
+ * one entry for each. bftsim_set_trace_twins (default 0; any value but 0 or 1 is BFTSIM_EINVAL) is read by the next
+ * bftsim_crypto_verify that runs with bftsim_set_trace_keep on (with keep off it has no effect): the kept trace then
+ * carries, immediately behind every equivocating PrePrepare (flag 4) and behind every wildcard Prepare / Commit
+ * (flag 2) of a valid block above height 0 whose proposer is one of the instance's Byzantine validators, one more
+ * frame, the twin: the same message (code, view, create_time, sender, signing key) for the block's other variant,
+ * with that variant's digest (header, for a PrePrepare), its own commit seal and its own signature. frame_meta word 2
+ * of a twin is its original's flags with bit 16 set; words 0, 1 and 3 are the original's. bftsim_trace_sizes,
+ * bftsim_export_trace, bftsim_audit_last_trace and bftsim_archive_last_trace see the twins in place. Twins are not
+ * log entries: the report and checksums of bftsim_crypto_verify, bftsim_export_ledger, bftsim_fetch and the statistics
+ * are the same with twins on and off. */
+int bftsim_set_trace_twins(bftsim_t *h, int on);
+/* the twins of the last kept trace: those of PrePrepares and those of votes (either may be NULL); 0 and 0 for a trace
+ * kept with twins off. BFTSIM_EINVAL, with nothing written, whenever bftsim_export_trace would refuse for lack of a
+ * kept trace. */
+int bftsim_trace_twin_counts(bftsim_t *h, uint64_t *pp_twins, uint64_t *vote_twins);
+/* diagnostics: device times (ms, HIP events) of the last verify's twin passes: mark + scan + merge (with the host's
+ * round trip for the count), the digest kernels, the signing; as scripts/trace_bench.py --twins records them */
+int bftsim_trace_twins_last_ms(bftsim_t *h, float *index_ms, float *digest_ms, float *sign_ms);
+
 /* the observer (SPEC.md §11c): a frame stream in the export's format, audited from its bytes on the device. Per frame:
  * decode (every read bounded by the frame's span in frame_off; the bytes are untrusted), the sign payload rebuilt from
  * the decoded fields with signature None, its signer recovered and looked up in the handle's validator set, and for a

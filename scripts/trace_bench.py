@@ -6,7 +6,11 @@ stage, 16-byte coalesced stores; the lane-per-frame emitter it was measured agai
 and records, from the library's HIP events, the emit kernel's frames/s and device-side GB/s, the device-to-host
 copy time, the size pass, and the wall time of the verify pass in the same process.
 
-    python scripts/trace_bench.py [--instances 1024] [--heights 10] [--repeats 5] [--out FILE.json]
+    python scripts/trace_bench.py [--instances 1024] [--heights 10] [--repeats 5] [--twins] [--out FILE.json]
+
+--twins (SPEC.md §11f): the verifies run with bftsim_set_trace_twins on, and the record gains the twin
+counts, their share of the frames, and per verify the device times of the twin passes (mark + scan + merge, digests,
+signing) next to the size pass and the emit kernel, which then run over the merged index.
 """
 import argparse
 import ctypes
@@ -27,6 +31,7 @@ def main():
     ap.add_argument("--instances", type=int, default=1024)
     ap.add_argument("--heights", type=int, default=10)
     ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--twins", action="store_true")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r07", "trace_export", "trace_bench.json"))
     args = ap.parse_args()
     from bftsim.configs import cfg3
@@ -38,20 +43,25 @@ def main():
     sim = Simulator(cfg)
     sim.set_crypto(secrets, (), 24_576)
     sim.set_trace_keep(True)
+    sim.set_trace_twins(args.twins)
     sim.prepare(args.instances)
-    verify_s = []
+    verify_s, twin_ms, size_each = [], [], []
     for _ in range(1 + args.repeats):                      # the first is the warm-up
         sim.launch(0)
         sim.sync()
         t0 = time.perf_counter()
         rep = sim.crypto_verify()
         verify_s.append(time.perf_counter() - t0)
+        twin_ms.append(sim.trace_twins_ms())
+        sim.trace_sizes()                                   # the size pass + scan of this verify's trace
+        size_each.append(sim.trace_ms()[0])
     assert rep["mismatches"] == 0 and rep["seal_errors"] == 0, rep
     t0 = time.perf_counter()
     fr, by = sim.trace_sizes()
     sizes_wall = time.perf_counter() - t0
     size_ms = sim.trace_ms()[0]
     frames, nbytes = int(fr.sum()), int(by.sum())
+    twins = sim.trace_twin_counts()
     stream, off = np.zeros(nbytes, np.uint8), np.zeros(frames + 1, np.uint64)
     rows = []
     for r in range(1 + args.repeats):
@@ -80,6 +90,18 @@ def main():
                messages=rep["messages"], seals=rep["seals"],
                verify_wall_ms=[round(1000 * x, 2) for x in verify_s[1:]], size_pass_ms=size_ms, sizes_call_wall_ms=1000 * sizes_wall,
                coop=summary(rows), stream_keccak256=dig.raw.hex())
+    out["size_pass_ms_each"] = [round(x, 4) for x in size_each[1:]]
+    if args.twins:
+        pp, votes = twins
+        med = lambda xs: sorted(xs)[len(xs) // 2]
+        t = dict(pp_twins=pp, vote_twins=votes, twin_share_of_frames=(pp + votes) / max(frames, 1),
+                 index_ms=[round(x[0], 4) for x in twin_ms[1:]], digest_ms=[round(x[1], 4) for x in twin_ms[1:]],
+                 sign_ms=[round(x[2], 4) for x in twin_ms[1:]])
+        t["median_ms"] = dict(index=med(t["index_ms"]), digest=med(t["digest_ms"]), sign=med(t["sign_ms"]),
+                              size=med(out["size_pass_ms_each"]), emit=out["coop"]["emit_ms_median"])
+        t["twin_passes_over_verify_wall"] = (t["median_ms"]["index"] + t["median_ms"]["digest"] + t["median_ms"]["sign"]) * 1e-3 / \
+            sorted(verify_s[1:])[len(verify_s[1:]) // 2]
+        out["twins"] = t
     vmed = sorted(verify_s[1:])[len(verify_s[1:]) // 2]
     out["emit_over_verify"] = out["coop"]["emit_ms_median"] * 1e-3 / vmed
     out["export_wall_over_verify"] = sorted(out["coop"]["wall_ms"])[len(out["coop"]["wall_ms"]) // 2] * 1e-3 / vmed
