@@ -343,6 +343,13 @@ def tamper_cases():
     outsider = seal(O.keccak256(b"not a validator"), block_hash(d4))
     swapped = list(L)
     swapped[1], swapped[2] = swapped[2], swapped[1]
+    # forged seals (tests/sig_cases.py): r + n = the first x of the curve above n, recovery id 2, which recovers over
+    # any digest, to a key outside the set; and one that recovers to the point at infinity over this very digest
+    import sig_cases as SC
+    high_x = SC.sig_of(0x5ea1 << 200, SC.high_x_points(1)[0][0])
+    to_inf = SC.forge_infinity(seal_digest(block_hash(d4)), 0xfeed << 190)
+    assert high_x[64] == 2 and O.secp_recover(seal_digest(block_hash(d4)), high_x) is not None
+    assert to_inf[64] < 2 and O.secp_recover(seal_digest(block_hash(d4)), to_inf) is None
     out = [("absent", c1, [L[:3]], 6, {(0, 4): ABSENT}),
            ("truncated", c1, [L[:2] + [L[2][:-5]] + L[3:]], 6, {(0, 3): UNDECODABLE, (0, 4): NO_PARENT}),
            ("height", c1, [L[:2] + [rs(L[2], height=7)] + L[3:]], 6, {(0, 3): BAD_HEIGHT}),
@@ -364,6 +371,8 @@ def tamper_cases():
            ("outsider", n4, [[with_votes(nil4, list(d4["votes"]) + [outsider])]], 6, {(0, 1): BAD_VOTE}),
            ("outsider alone", n4, [[with_votes(nil4, [outsider])]], 6, {(0, 1): BAD_VOTE}),
            ("unrecoverable", n4, [[with_votes(nil4, [bytes(65)] * 3)]], 6, {(0, 1): BAD_VOTE}),
+           ("forged high-x seal", n4, [[with_votes(nil4, list(d4["votes"]) + [high_x])]], 6, {(0, 1): BAD_VOTE}),
+           ("seal to infinity", n4, [[with_votes(nil4, list(d4["votes"]) + [to_inf])]], 6, {(0, 1): BAD_VOTE}),
            ("trailing", n4, [[h4 + b"\x00"], [with_votes(nil4, [d4["votes"][0][:64]])],
                              [nil4[:-1] + msgpack.packb([list(d4["votes"][0])] * 257)],
                              [with_votes(nil4, [d4["votes"][0]] * 256)]], 1,
