@@ -9,7 +9,9 @@ import msgpack
 import pytest
 
 import oracle_lib as O
-from bftsim.configs import cfg1, string_to_address
+import time_cases as T
+from bftsim.configs import BftConfig, cfg1, string_to_address
+from time_cases import GRID_HASHES, GRID_HEIGHTS, GRID_TIMES
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 KAT = json.load(open(os.path.join(GOLD, "kat.json")))
@@ -107,6 +109,48 @@ def test_header_encoding_matches_python_msgpack():
     buf = (ctypes.c_uint8 * 512)()
     n = O.lib().orc_encode_header(buf, prev, prop, tx, 7, 0, 0, 1536517092, extra, len(extra))
     assert bytes(buf[:n]) == want
+
+
+# the genesis time of every row of tests/time_cases.py (t-top: the largest that cannot wrap at N = 4, 40 heights)
+TABLE_GENESIS = [T.with_time(BftConfig(n=4, heights=40), k).genesis_time for k in T.IDS]
+
+
+def msgpack_header(prev, prop, tx, height, time, extra=b"Coinse base", gas_limit=0, gas_used=0):
+    return msgpack.packb([list(prev), "0x" + prop.hex(), [0] * 32, list(tx), [0] * 32, 0, 0, height, gas_limit, gas_used,
+                          time, list(extra), None], use_bin_type=True)
+
+
+@pytest.mark.parametrize("time", GRID_TIMES)
+def test_header_encoding_at_every_width_of_height_and_time(time):
+    """SPEC.md §7 at every MessagePack width boundary of `height` and `time`, parents and tx hashes of all-high and
+    all-low bytes (the shortest and the longest header): the oracle's encoder against the msgpack package"""
+    prop = string_to_address("0x72d5c75fd6703414aa87f79b3e4797dd09cd9251")
+    extra = b"Coinse base"
+    L = O.lib()
+    sizes = set()
+    for height in GRID_HEIGHTS:
+        for prev in GRID_HASHES:
+            for tx in GRID_HASHES:
+                buf = (ctypes.c_uint8 * 512)()
+                n = L.orc_encode_header(buf, prev, prop, tx, height, 0, 0, time, extra, len(extra))
+                assert bytes(buf[:n]) == msgpack_header(prev, prop, tx, height, time), (height, time)
+                sizes.add(n)
+    assert len(sizes) == 3 * 4                                    # 3 lengths of the hashes x 4 widths of the height
+
+
+@pytest.mark.parametrize("genesis_time,gas_used",
+                         [(t, 10000) for t in TABLE_GENESIS] +
+                         [(1536517089, g) for g in (0, 117, 118, 245, 246, 65525, 65526)])
+def test_genesis_hash_at_every_width(genesis_time, gas_used):
+    """orc_genesis_hash against msgpack + Keccak at the genesis times of tests/time_cases.py and with
+    gas_limit = gas_used + 10 on both sides of 127/128, 255/256 and 65535/65536"""
+    import dataclasses
+    c = dataclasses.replace(cfg1(True), genesis_time=genesis_time, genesis_gas_used=gas_used)
+    c_, keep = O.to_orc(c)
+    out = (ctypes.c_uint8 * 32)()
+    O.lib().orc_genesis_hash(ctypes.byref(c_), out)
+    enc = msgpack_header(bytes(32), c.genesis_proposer, bytes(32), 0, genesis_time, b"Hello Word!", gas_used + 10, gas_used)
+    assert bytes(out) == _py_keccak256(enc)
 
 
 def test_genesis_hash_fixture():
