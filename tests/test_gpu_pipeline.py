@@ -228,7 +228,12 @@ def test_predicted_chains_match_oracle(name, mk, depth, batch, monkeypatch):
     blocks from launch time on; the recorded blocks are checked against the predictions and the chains re-run from
     the first one that differs. Lossless cfg3 (every prediction right), drops and forks (the repair from a height
     inside the chain), proposer crashes and a silent validator 0 (wrong from height 1: the whole chain repaired).
-    12 launches of the same instances, with predictions on and off, against the oracle."""
+    12 launches of the same instances, with predictions on and off, against the oracle.
+    These relaunch one range and compare the last launch: the set it reuses already holds these instances' rows,
+    hashes and predictions, so its stale rows equal the fresh ones and a skipped repair of a reused set would pass
+    here. The repair under reuse -- distinct ranges, every launch compared -- is tests/test_gpu_set_reuse.py's; its
+    oracle check (tests/reuse_cases.py) also shows that n64-drop and n64-fork stay on the canonical tick (proposer 0
+    at tick height - 1) and can miss a prediction only on the variant, while n64-crash misses in every instance."""
     monkeypatch.setenv("BFTSIM_TESTING", "1")
     cfg = mk()
     n = 96
@@ -291,7 +296,9 @@ def test_predicted_lane_chains_sweep(seed, byz, drop, crash, heights, monkeypatc
     """Predicted LANE chains (DESIGN §4j: each lane predicts, masks and encodes its blocks; 56-dword LDS columns;
     the register-resident prefix) over seeds, Byzantine counts (0 .. 42), drops and proposer crashes, forced at a
     small size (BFTSIM_CHAIN_LANE_MIN=1; BFTSIM_HASH_SPEC=2: lossy schedules too), 9 launches in batches of 4,
-    every instance against the oracle."""
+    every instance against the oracle.
+    The 9 launches are of one range and the last is compared: when the ring of 8 sets wraps, the reused set's stale
+    rows equal the fresh ones. The repair over another range's rows is tests/test_gpu_set_reuse.py's."""
     monkeypatch.setenv("BFTSIM_TESTING", "1")
     monkeypatch.setenv("BFTSIM_CHAIN_LANE_MIN", "1")
     monkeypatch.setenv("BFTSIM_HASH_SPEC", "2")

@@ -102,7 +102,8 @@ def test_windowed_stream(case):
     assert not (got["flags"] & 64).any()
 
 
-# ---- c. pipelined chain kernels: 5 launches over distinct ranges (the ring wraps), the last one compared
+# ---- c. pipelined chain kernels: 5 launches over distinct ranges, the last one compared (the ring wraps at depth 3
+# only; the depth-6 modes reuse no set, time_cases.CHAIN_MODES)
 def _chain(mode, case, monkeypatch):
     _, _, depth, batch, env = T.CHAIN_MODES[mode]
     monkeypatch.setenv("BFTSIM_TESTING", "1")

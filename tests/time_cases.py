@@ -35,7 +35,9 @@ GRID_HEIGHTS = WIDTH_EDGES
 GRID_TIMES = WIDTH_EDGES + [2 ** 32, 2 ** 64 - 1]
 GRID_HASHES = [bytes(range(200, 232)), bytes(range(0, 32))]        # all-high (two bytes each) and all-low
 
-# ---- pipelined chain kernels (N = 64): 5 launches over distinct ranges (the ring wraps), the last one compared.
+# ---- pipelined chain kernels (N = 64): 5 launches over distinct ranges, the last one compared. Only the depth-3 modes
+# (wave, pair: lossless cfg3) come back to a set; at depth 6 five launches reuse none, so the lossy modes here show
+# the widths, not a repair over another instance's rows (tests/test_gpu_set_reuse.py has those).
 # name -> (config of _shapes' chain_cfg, instances, depth, hash batch or 0, environment under BFTSIM_TESTING=1).
 # The library does not report which chain kernel a launch ran: these settings select the modes only as long as
 # bftsim.hip's knobs and thresholds (chain_wave_max, chain_lane_min, chain_inline, chain_grid, hash_spec, seed_spec)
