@@ -71,6 +71,34 @@ class CArchiveOut(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in ("status", "pp_frame", "n_votes", "archived_height")]
 
 
+class CAccuseReport(ctypes.Structure):
+    _fields_ = [("records", ctypes.c_uint64), ("by_code", ctypes.c_uint64 * 3)] + [(k, ctypes.c_uint64) for k in (
+        "accused", "accused_instances", "view_overflows")]
+
+
+class CAccuseOut(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in ("frame_pair", "inst_accused", "inst_flags", "records")] + [
+        ("rec_cap", ctypes.c_uint64)]
+
+
+# bftsim_accuse_record
+ACCUSE_RECORD = np.dtype([("round", "<u8"), ("inst", "<u4"), ("height", "<u4"), ("signer", "<u4"), ("code", "<u4"),
+                          ("frame_a", "<u4"), ("frame_b", "<u4")])
+
+
+def alloc_accuse(frames: int, n_inst: int, rec_cap: int = None):
+    """host buffers of bftsim_accuse_out -> (struct, arrays). rec_cap: frames by default (a frame closes one record at
+    most, so no second call is ever needed; the pages of an np.empty cost nothing until they are written)"""
+    cap = frames if rec_cap is None else rec_cap
+    arrs = dict(frame_pair=np.full(frames, 0xffffffff, np.uint32), inst_accused=np.zeros(n_inst * 4, np.uint64),
+                inst_flags=np.zeros(n_inst, np.uint32), records=np.empty(cap, ACCUSE_RECORD))
+    o = CAccuseOut()
+    for k, a in arrs.items():
+        setattr(o, k, a.ctypes.data if a.size else None)
+    o.rec_cap = cap
+    return o, arrs
+
+
 def alloc_archive(n_inst: int, heights: int, slot_bytes: int):
     """host buffers of bftsim_archive_trace: the header slots, their lengths and bftsim_archive_out -> (hdr, hdr_len,
     struct, arrays)"""

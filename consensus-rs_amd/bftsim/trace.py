@@ -142,6 +142,35 @@ class Audit:
         return out
 
 
+ACCUSE_NONE = 0xffffffff
+ACCUSE_VIEW_OVERFLOW = 1
+
+
+class Accusation:
+    """What the accuser made of a frame stream (SPEC.md §11g): records, a structured array (round, inst, height,
+    signer, code, frame_a, frame_b; one per (signer, code, height, round) that carries two digests, ascending frame_b,
+    the frame indices among the call's frames); frame_pair [frames] u32 (frame_a of the record a frame closes, else
+    ACCUSE_NONE); inst_accused [n, 4] u64; inst_flags [n] u32; report: bftsim_accuse_report as a dict (records: all
+    that were found, also when rec_cap kept fewer); audit: the observer's outputs of the same call."""
+
+    def __init__(self, arrs: dict, rep, n: int, audit: Audit = None):
+        self.n, self.audit = n, audit
+        self.frame_pair, self.inst_flags = arrs["frame_pair"], arrs["inst_flags"]
+        self.inst_accused = arrs["inst_accused"].reshape(n, 4)
+        self.report = {k: (list(getattr(rep, k)) if k == "by_code" else int(getattr(rep, k))) for k, _ in rep._fields_}
+        self.records = arrs["records"][:min(self.report["records"], len(arrs["records"]))]
+
+    def accused(self, i: int) -> list:
+        """validator indices accused in instance i, ascending"""
+        w = self.inst_accused[i]
+        return [v for v in range(256) if (int(w[v >> 6]) >> (v & 63)) & 1]
+
+    def proof(self, trace, k: int) -> tuple:
+        """the two frames' bytes of record k, out of the trace the call ran over: (frame_a, frame_b)"""
+        r = self.records[k]
+        return trace.frame(int(r["frame_a"])), trace.frame(int(r["frame_b"]))
+
+
 def compare(audit: Audit, result: dict, begin: int = 0) -> dict:
     """The certificates against a run's result (Simulator.run / fetch; audit instance i = result instance begin + i).
     Per instance, over the committed heights: `certified` with a certificate for the committed hash, `missing`

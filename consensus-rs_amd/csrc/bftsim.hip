@@ -32,6 +32,7 @@
 #include "bft_twins.h"
 #include "bft_audit.h"
 #include "bft_archive.h"
+#include "bft_accuse.h"
 #include "bft_ledger.h"
 
 namespace bft {
@@ -675,6 +676,7 @@ struct bftsim {
     double acc_c = 0, acc_h = 0;
     uint32_t acc_n = 0;
     float archive_ms[4] = {0, 0, 0, 0};// the observer's passes, pick, emit + heights, copies of the last archive (SPEC.md §11e)
+    float accuse_ms[4] = {0, 0, 0, 0}; // the observer's passes, walk, mark + scan + gather, copies of the last accuse (SPEC.md §11g)
 };
 
 static int fail(bftsim* h, int code, const std::string& msg) {
@@ -2371,12 +2373,103 @@ static int archive_copy(bftsim* h, ArchiveCont& ac, const uint8_t* p, uint64_t i
     rep->archived_instances = ac.counts[R::CNT_ARCHIVED];
     return BFTSIM_OK;
 }
+// ---- the accuser (SPEC.md §11g): a continuation of audit_device like the archiver's, run after the classify and
+// tally passes over their records, statuses and signers, which it only reads. Its tables are one more piece of the pool.
+namespace {
+struct AccuseCont {
+    uint32_t view_cap;
+    const bftsim_accuse_out* out;     // the caller's
+    bftsim_accuse_report* report;
+    uint64_t rec_cap, bytes, o_views, o_first, o_pair, o_acc, o_flags, o_mark, o_pos, o_recs, o_counts, o_scan;
+    size_t scan_bytes;
+    unsigned long long counts[bft::accuse::CNT_WORDS];
+    uint32_t total;                   // the scan's
+    float ms[2];                      // walk, mark + scan + gather
+};
+}  // namespace
+static int accuse_layout(bftsim* h, AccuseCont& xc, uint64_t frames, uint64_t inst, uint32_t max_heights) {
+    namespace X = bft::accuse;
+    const uint64_t Fx = frames ? frames : 1, Ix = inst ? inst : 1;
+    if (xc.view_cap == 0) xc.view_cap = X::default_view_cap(max_heights);
+    const uint64_t per_view = sizeof(X::View) + 12ull * h->cfg.n;
+    if (xc.view_cap > (1ull << 40) / per_view / Ix)
+        return fail(h, BFTSIM_ENOMEM, "bftsim_accuse: view_cap x instances above 1 TiB of view tables");
+    if (frames >= (1ull << 31) - 1) return fail(h, BFTSIM_ENOMEM, "bftsim_accuse: 2^31 frames or more");    // the scan's int
+    xc.rec_cap = xc.out->records ? (xc.out->rec_cap < frames ? xc.out->rec_cap : frames) : 0;   // a frame closes one record at most
+    uint64_t bytes = 0;
+    auto sized = [&](uint64_t b) { const uint64_t o = bytes; bytes += (b + 31) & ~31ull; return o; };
+    xc.o_views = sized(Ix * xc.view_cap * sizeof(X::View));
+    xc.o_first = sized(Ix * xc.view_cap * 12ull * h->cfg.n);
+    xc.o_pair = sized(Fx * 4);
+    xc.o_acc = sized(Ix * 32); xc.o_flags = sized(Ix * 4);
+    xc.o_mark = sized((Fx + 1) * 4); xc.o_pos = sized((Fx + 1) * 4);
+    xc.o_recs = sized((xc.rec_cap ? xc.rec_cap : 1) * sizeof(X::Record));
+    xc.o_counts = sized(X::CNT_WORDS * 8);
+    xc.scan_bytes = 0;
+    HIPCHECK(h, hipcub::DeviceScan::ExclusiveSum(nullptr, xc.scan_bytes, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)(frames + 1)));
+    xc.o_scan = sized(xc.scan_bytes ? xc.scan_bytes : 1);
+    xc.bytes = bytes;
+    return BFTSIM_OK;
+}
+static int accuse_passes(bftsim* h, AccuseCont& xc, uint8_t* p, uint64_t frames, const bft::audit::Recs& r,
+                         const uint8_t* d_status, const int32_t* d_signer, const uint64_t* d_if0, uint64_t inst, hipStream_t s) {
+    namespace X = bft::accuse;
+    const X::Args a{r, d_status, d_signer, d_if0, frames, inst, h->cfg.n, xc.view_cap, (X::View*)(p + xc.o_views),
+                    (uint32_t*)(p + xc.o_first), (uint32_t*)(p + xc.o_pair), (uint64_t*)(p + xc.o_acc),
+                    (uint32_t*)(p + xc.o_flags), (uint32_t*)(p + xc.o_mark), (uint32_t*)(p + xc.o_pos),
+                    (X::Record*)(p + xc.o_recs), xc.rec_cap, (unsigned long long*)(p + xc.o_counts)};
+    Events ev;
+    HIPCHECK(h, ev.create(3));
+    HIPCHECK(h, hipMemsetAsync(p + xc.o_first, 0xff, xc.o_acc - xc.o_first, s));      // NONE: first and frame_pair
+    HIPCHECK(h, hipMemsetAsync(p + xc.o_acc, 0, xc.o_mark - xc.o_acc, s));            // instances without a wave
+    HIPCHECK(h, hipMemsetAsync(p + xc.o_counts, 0, X::CNT_WORDS * 8, s));
+    HIPCHECK(h, hipEventRecord(ev[0], s));
+    HIPCHECK(h, X::launch_walk(a, s));
+    HIPCHECK(h, hipEventRecord(ev[1], s));
+    HIPCHECK(h, X::launch_mark(a, s));
+    HIPCHECK(h, hipcub::DeviceScan::ExclusiveSum(p + xc.o_scan, xc.scan_bytes, a.mark, a.pos, (int)(frames + 1), s));
+    HIPCHECK(h, X::launch_gather(a, s));
+    HIPCHECK(h, hipEventRecord(ev[2], s));
+    HIPCHECK(h, hipMemcpyAsync(xc.counts, p + xc.o_counts, sizeof xc.counts, hipMemcpyDeviceToHost, s));
+    HIPCHECK(h, hipMemcpyAsync(&xc.total, a.pos + frames, 4, hipMemcpyDeviceToHost, s));
+    HIPCHECK(h, hipStreamSynchronize(s));
+    for (int k = 0; k < 2; ++k) HIPCHECK(h, hipEventElapsedTime(&xc.ms[k], ev[k], ev[k + 1]));
+    if (xc.total != xc.counts[X::CNT_RECORDS])
+        return fail(h, BFTSIM_EHIP, "bftsim_accuse: the scan's total disagrees with the walk's count");
+    return BFTSIM_OK;
+}
+static int accuse_copy(bftsim* h, AccuseCont& xc, const uint8_t* p, uint64_t frames, uint64_t inst, hipStream_t s) {
+    namespace X = bft::accuse;
+    const uint64_t written = xc.total < xc.rec_cap ? xc.total : xc.rec_cap;
+    Events ev;
+    HIPCHECK(h, ev.create(2));
+    HIPCHECK(h, hipEventRecord(ev[0], s));
+    const struct { void* dst; uint64_t off, b; } back[] = {
+        {xc.out->frame_pair, xc.o_pair, frames * 4}, {xc.out->inst_accused, xc.o_acc, inst * 32},
+        {xc.out->inst_flags, xc.o_flags, inst * 4}, {xc.out->records, xc.o_recs, written * sizeof(X::Record)}};
+    for (const auto& k : back)
+        if (k.dst && k.b) HIPCHECK(h, hipMemcpyAsync(k.dst, p + k.off, k.b, hipMemcpyDeviceToHost, s));
+    HIPCHECK(h, hipEventRecord(ev[1], s));
+    HIPCHECK(h, hipStreamSynchronize(s));
+    float copy_ms = 0;
+    HIPCHECK(h, hipEventElapsedTime(&copy_ms, ev[0], ev[1]));
+    h->accuse_ms[0] = h->audit_ms[0] + h->audit_ms[1] + h->audit_ms[2];
+    h->accuse_ms[1] = xc.ms[0]; h->accuse_ms[2] = xc.ms[1]; h->accuse_ms[3] = h->audit_ms[3] + copy_ms;
+    bftsim_accuse_report* rep = xc.report;
+    memset(rep, 0, sizeof *rep);
+    rep->records = xc.counts[X::CNT_RECORDS];
+    for (int k = 0; k < 3; ++k) rep->by_code[k] = xc.counts[X::CNT_CODE + k];
+    rep->accused = xc.counts[X::CNT_ACCUSED];
+    rep->accused_instances = xc.counts[X::CNT_INSTANCES];
+    rep->view_overflows = xc.counts[X::CNT_VIEW_OVERFLOWS];
+    return BFTSIM_OK;
+}
 // the passes over a device stream: frame k = d_stream[d_foff[k] - base, d_foff[k + 1] - base),
 // if0 on the host. Every temporary is freed before returning; only the caller's buffers and h->audit_ms are written.
 static int audit_device(bftsim* h, const uint8_t* d_stream, const uint64_t* d_foff, uint64_t base, uint64_t frames,
                         const uint64_t* if0, uint64_t inst, uint32_t max_heights, uint32_t key_cap,
                         const bftsim_audit_out* out, bftsim_audit_report* report, hipStream_t s, float copy_in_ms,
-                        ArchiveCont* ac = nullptr) {
+                        ArchiveCont* ac = nullptr, AccuseCont* xc = nullptr) {
     namespace A = bft::audit;
     SigApi& sa = sig_api();
     if (key_cap == 0) key_cap = 4u * max_heights + 64u;
@@ -2396,6 +2489,11 @@ static int audit_device(bftsim* h, const uint8_t* d_stream, const uint64_t* d_fo
     if (ac) {                                                                      // the archiver's tables and slots
         if (int rc = archive_layout(h, *ac, inst, max_heights)) return rc;
         bytes += ac->bytes;
+    }
+    const uint64_t o_accuse = bytes;
+    if (xc) {                                                                      // the accuser's tables
+        if (int rc = accuse_layout(h, *xc, F, inst, max_heights)) return rc;
+        bytes += xc->bytes;
     }
     DevMem pool_mem;
     if (pool_mem.alloc(bytes) != hipSuccess)
@@ -2447,6 +2545,8 @@ static int audit_device(bftsim* h, const uint8_t* d_stream, const uint64_t* d_fo
                                     max_heights, certs, s))
             return rc;
     }
+    if (xc)
+        if (int rc = accuse_passes(h, *xc, pool + o_accuse, F, r, d_status, d_signer, d_if0, inst, s)) return rc;
     if (out) {
         const struct { void* dst; uint64_t off, b; } back[] = {
             {out->frame_status, o_status, F}, {out->frame_signer, o_signer, F * 4}, {out->inst_flags, o_iflags, inst * 4},
@@ -2471,6 +2571,7 @@ static int audit_device(bftsim* h, const uint8_t* d_stream, const uint64_t* d_fo
     report->conflicts = c[A::CNT_CONFLICTS];
     report->key_overflows = c[A::CNT_KEY_OVERFLOWS];
     report->recoveries = F + n_seals;
+    if (xc) return accuse_copy(h, *xc, pool + o_accuse, F, inst, s);
     return ac ? archive_copy(h, *ac, pool + o_arch, inst, max_heights, s) : BFTSIM_OK;
 }
 static int audit_dims(bftsim* h, uint64_t frames, uint64_t inst, uint32_t max_heights, const char* what) {
@@ -2483,7 +2584,8 @@ static int audit_dims(bftsim* h, uint64_t frames, uint64_t inst, uint32_t max_he
 // the observer over a host stream; ac: the archiver's continuation (null for bftsim_audit_trace)
 static int audit_host_stream(bftsim* h, const uint8_t* stream, uint64_t stream_bytes, const uint64_t* frame_off, uint64_t frames,
                              const uint64_t* inst_frame0, uint64_t inst_count, uint32_t max_heights, uint32_t key_cap,
-                             const bftsim_audit_out* out, bftsim_audit_report* report, ArchiveCont* ac) {
+                             const bftsim_audit_out* out, bftsim_audit_report* report, ArchiveCont* ac,
+                             AccuseCont* xc = nullptr) {
     if (!frame_off || !inst_frame0 || (stream_bytes && !stream))
         return fail(h, BFTSIM_EINVAL, "bftsim_audit_trace: null stream, frame_off or inst_frame0");
     if (int rc = audit_dims(h, frames, inst_count, max_heights, "bftsim_audit_trace")) return rc;
@@ -2512,7 +2614,7 @@ static int audit_host_stream(bftsim* h, const uint8_t* stream, uint64_t stream_b
     HIPCHECK(h, hipStreamSynchronize(s));
     HIPCHECK(h, hipEventElapsedTime(&copy_ms, ev[0], ev[1]));
     return audit_device(h, d_in, (const uint64_t*)(d_in + sb + 16), 0, frames, inst_frame0, inst_count, max_heights, key_cap,
-                        out, report, s, copy_ms, ac);
+                        out, report, s, copy_ms, ac, xc);
 }
 int bftsim_audit_trace(bftsim_t* h, const uint8_t* stream, uint64_t stream_bytes, const uint64_t* frame_off, uint64_t frames,
                        const uint64_t* inst_frame0, uint64_t inst_count, uint32_t max_heights, uint32_t key_cap,
@@ -2524,7 +2626,8 @@ int bftsim_audit_trace(bftsim_t* h, const uint8_t* stream, uint64_t stream_bytes
 
 // the observer over the kept trace of the last launch; ac as above
 static int audit_kept_trace(bftsim* h, uint64_t inst_begin, uint64_t inst_count, uint32_t key_cap,
-                            const bftsim_audit_out* out, bftsim_audit_report* report, ArchiveCont* ac) {
+                            const bftsim_audit_out* out, bftsim_audit_report* report, ArchiveCont* ac,
+                            AccuseCont* xc = nullptr) {
     if (int rc = trace_ready(h, "bftsim_audit_last_trace")) return rc;
     const uint64_t n = h->trace_n;
     if (inst_begin > n || inst_count > n - inst_begin)
@@ -2545,7 +2648,7 @@ static int audit_kept_trace(bftsim* h, uint64_t inst_begin, uint64_t inst_count,
         return fail(h, BFTSIM_ENOMEM, "bftsim_audit_last_trace: device memory for the stream");
     if (int rc = trace_emit(h, "bftsim_audit_last_trace", m0, m1, d_out.as<uint8_t>(), nullptr, nullptr)) return rc;
     return audit_device(h, d_out.as<uint8_t>(), h->d_tfoff + m0, base, frames, if0.data(), inst_count, h->cfg.heights,
-                        key_cap, out, report, s, 0.f, ac);
+                        key_cap, out, report, s, 0.f, ac, xc);
 }
 int bftsim_audit_last_trace(bftsim_t* h, uint64_t inst_begin, uint64_t inst_count, uint32_t key_cap,
                             const bftsim_audit_out* out, bftsim_audit_report* report) {
@@ -2597,6 +2700,43 @@ int bftsim_archive_last_ms(bftsim_t* h, float* audit_ms, float* pick_ms, float* 
     if (pick_ms) *pick_ms = h->archive_ms[1];
     if (emit_ms) *emit_ms = h->archive_ms[2];
     if (copy_ms) *copy_ms = h->archive_ms[3];
+    return BFTSIM_OK;
+}
+
+// ---- the accuser's entry points (SPEC.md §11g): the observer's passes and refusals, then walk, mark, scan and gather
+static int accuse_args(bftsim* h, const bftsim_accuse_out* out, const char* what) {
+    if (!out) return fail(h, BFTSIM_EINVAL, std::string(what) + ": null out");
+    if (out->rec_cap && !out->records) return fail(h, BFTSIM_EINVAL, std::string(what) + ": rec_cap without records");
+    return BFTSIM_OK;
+}
+int bftsim_accuse_trace(bftsim_t* h, const uint8_t* stream, uint64_t stream_bytes, const uint64_t* frame_off, uint64_t frames,
+                        const uint64_t* inst_frame0, uint64_t inst_count, uint32_t max_heights, uint32_t key_cap,
+                        uint32_t view_cap, const bftsim_accuse_out* out, const bftsim_audit_out* audit_out,
+                        bftsim_audit_report* audit_report, bftsim_accuse_report* report) {
+    if (!h || !report) return BFTSIM_EINVAL;
+    if (int rc = accuse_args(h, out, "bftsim_accuse_trace")) return rc;
+    AccuseCont xc{};
+    xc.view_cap = view_cap; xc.out = out; xc.report = report;
+    bftsim_audit_report own;
+    return audit_host_stream(h, stream, stream_bytes, frame_off, frames, inst_frame0, inst_count, max_heights, key_cap,
+                             audit_out, audit_report ? audit_report : &own, nullptr, &xc);
+}
+int bftsim_accuse_last_trace(bftsim_t* h, uint64_t inst_begin, uint64_t inst_count, uint32_t key_cap, uint32_t view_cap,
+                             const bftsim_accuse_out* out, const bftsim_audit_out* audit_out,
+                             bftsim_audit_report* audit_report, bftsim_accuse_report* report) {
+    if (!h || !report) return BFTSIM_EINVAL;
+    if (int rc = accuse_args(h, out, "bftsim_accuse_last_trace")) return rc;
+    AccuseCont xc{};
+    xc.view_cap = view_cap; xc.out = out; xc.report = report;
+    bftsim_audit_report own;
+    return audit_kept_trace(h, inst_begin, inst_count, key_cap, audit_out, audit_report ? audit_report : &own, nullptr, &xc);
+}
+int bftsim_accuse_last_ms(bftsim_t* h, float* audit_ms, float* walk_ms, float* compact_ms, float* copy_ms) {
+    if (!h) return BFTSIM_EINVAL;
+    if (audit_ms) *audit_ms = h->accuse_ms[0];
+    if (walk_ms) *walk_ms = h->accuse_ms[1];
+    if (compact_ms) *compact_ms = h->accuse_ms[2];
+    if (copy_ms) *copy_ms = h->accuse_ms[3];
     return BFTSIM_OK;
 }
 

@@ -403,6 +403,54 @@ int bftsim_archive_last_trace(bftsim_t *h, uint64_t inst_begin, uint64_t inst_co
  * records them */
 int bftsim_archive_last_ms(bftsim_t *h, float *audit_ms, float *pick_ms, float *emit_ms, float *copy_ms);
 
+/* the accuser (SPEC.md §11g): who misbehaved, and what proves it. The observer's passes, then per instance over the
+ * frames it accepts (status OK or SEAL_FOREIGN) that are a PrePrepare, Prepare or Commit at a height in 1..max_heights:
+ * a group is (signer, code, height, round), the round as the full u64; a group whose frames carry two digests yields one
+ * evidence record, frame_a the group's first frame in stream order and frame_b its first frame with another digest.
+ * The two frames prove the fault to anyone who has the validator set: both decode, both recover to the same validator,
+ * and they differ in the digest alone among (code, height, round, digest). Further digests and repeats add nothing.
+ * Records are ordered by frame_b ascending. */
+#define BFTSIM_ACCUSE_VIEW_OVERFLOW 1u /* instance flag: a frame's (height, round) was absent from a full view table:
+                                          the frame was ignored */
+struct bftsim_accuse_record {       /* 32 bytes; frame_a < frame_b, both indices among the call's frames */
+    uint64_t round;
+    uint32_t inst, height, signer, code, frame_a, frame_b;
+};
+typedef struct bftsim_accuse_record bftsim_accuse_record;
+struct bftsim_accuse_report {
+    uint64_t records;               /* evidence records found (of which min(records, rec_cap) were written) */
+    uint64_t by_code[3];            /* of PrePrepares, Prepares, Commits */
+    uint64_t accused;               /* (instance, validator) pairs accused: the popcounts of inst_accused */
+    uint64_t accused_instances;     /* instances with a record */
+    uint64_t view_overflows;        /* instances with BFTSIM_ACCUSE_VIEW_OVERFLOW */
+};
+typedef struct bftsim_accuse_report bftsim_accuse_report;
+struct bftsim_accuse_out {          /* host, caller-owned, any pointer may be NULL */
+    uint32_t *frame_pair;           /* [frames] frame_a of the record whose frame_b this frame is, else 0xffffffff */
+    uint64_t *inst_accused;         /* [inst_count * 4] bitmap of the validators that sign a record of the instance */
+    uint32_t *inst_flags;           /* [inst_count] BFTSIM_ACCUSE_VIEW_OVERFLOW */
+    bftsim_accuse_record *records;  /* [rec_cap] the first min(report.records, rec_cap) records */
+    uint64_t rec_cap;               /* 0 with records NULL */
+};
+typedef struct bftsim_accuse_out bftsim_accuse_out;
+/* stream .. key_cap, audit_out and audit_report (both nullable): as bftsim_audit_trace, whose refusals are this call's
+ * and whose outputs those two receive unchanged. view_cap: (height, round) pairs per instance's table (0 =
+ * 2 * max_heights + 64); nothing is evicted. BFTSIM_EINVAL too for a null out or report and for a rec_cap above 0 with
+ * records NULL; BFTSIM_ENOMEM, before anything is launched, for tables the device cannot hold. A refused call writes
+ * nothing; hostile frame contents are never an error; the handle's run state is untouched; no secrets are needed. */
+int bftsim_accuse_trace(bftsim_t *h, const uint8_t *stream, uint64_t stream_bytes, const uint64_t *frame_off, uint64_t frames,
+                        const uint64_t *inst_frame0, uint64_t inst_count, uint32_t max_heights, uint32_t key_cap,
+                        uint32_t view_cap, const bftsim_accuse_out *out, const bftsim_audit_out *audit_out,
+                        bftsim_audit_report *audit_report, bftsim_accuse_report *report);
+/* the same over the kept trace of the last launch, as bftsim_audit_last_trace: the stream never leaves the device */
+int bftsim_accuse_last_trace(bftsim_t *h, uint64_t inst_begin, uint64_t inst_count, uint32_t key_cap, uint32_t view_cap,
+                             const bftsim_accuse_out *out, const bftsim_audit_out *audit_out,
+                             bftsim_audit_report *audit_report, bftsim_accuse_report *report);
+/* diagnostics: device times (ms, HIP events) of the last accuse call: the observer's passes (decode, recoveries,
+ * classification + tally), the walk kernel, mark + scan + gather, and the copies, as scripts/accuse_bench.py records
+ * them */
+int bftsim_accuse_last_ms(bftsim_t *h, float *audit_ms, float *walk_ms, float *compact_ms, float *copy_ms);
+
 /* the importer (SPEC.md §11d): what a syncing node runs on every Header it is handed, Engine::verify_header with
  * seal = true and verify_seal (src/consensus/backend.rs:319-367), batched: every header of every instance's ledger,
  * verified from untrusted bytes on the device.
