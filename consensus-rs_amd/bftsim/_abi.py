@@ -99,6 +99,35 @@ def alloc_accuse(frames: int, n_inst: int, rec_cap: int = None):
     return o, arrs
 
 
+class CTimelineReport(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_uint64) for k in (
+        "prepare_frames", "rc_frames", "out_of_range", "prepared", "rc_quorums", "rc_heights", "prepared_first",
+        "cert_unprepared", "locked_open", "key_overflows")]
+
+
+# bftsim_timeline_out: field -> (dtype, words per row, preset); the last two per instance, the others per row
+TIMELINE_ROWS = dict(prep_round=(np.uint16, 1, 0xffff), prep_digest=(np.uint8, 32, 0), prep_voters=(np.uint64, 4, 0),
+                     prep_frame=(np.uint32, 1, 0), prep_quorums=(np.uint16, 1, 0), rc_quorums=(np.uint16, 1, 0),
+                     rc_max_round=(np.uint16, 1, 0xffff), rc_max_frame=(np.uint32, 1, 0), rc_top_round=(np.uint16, 1, 0xffff),
+                     rc_frames=(np.uint32, 1, 0), flags=(np.uint8, 1, 0))
+TIMELINE_INST = ("inst_flags", "open_height")
+
+
+class CTimelineOut(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in tuple(TIMELINE_ROWS) + TIMELINE_INST]
+
+
+def alloc_timeline(n_inst: int, heights: int):
+    """host buffers of bftsim_timeline_out -> (struct, arrays)"""
+    rows = n_inst * heights
+    arrs = {k: np.full(rows * w, fill, dt) for k, (dt, w, fill) in TIMELINE_ROWS.items()}
+    arrs.update(inst_flags=np.zeros(n_inst, np.uint32), open_height=np.full(n_inst, heights + 1, np.uint32))
+    o = CTimelineOut()
+    for k, a in arrs.items():
+        setattr(o, k, a.ctypes.data if a.size else None)
+    return o, arrs
+
+
 def alloc_archive(n_inst: int, heights: int, slot_bytes: int):
     """host buffers of bftsim_archive_trace: the header slots, their lengths and bftsim_archive_out -> (hdr, hdr_len,
     struct, arrays)"""

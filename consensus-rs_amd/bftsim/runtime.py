@@ -90,6 +90,13 @@ def lib():
             L.bftsim_accuse_trace.argtypes = L.bftsim_audit_trace.argtypes[:9] + tail
             L.bftsim_accuse_last_trace.argtypes = L.bftsim_audit_last_trace.argtypes[:4] + tail
             L.bftsim_accuse_last_ms.argtypes = [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_float)] * 4
+        if not os.environ.get("BFTSIM_LIB") or hasattr(L, "bftsim_timeline_trace"):
+            # (an A/B build of an earlier commit may lack them, scripts/timeline_bench.py --parent-lib; the product must not)
+            tail = [ctypes.c_uint32, ctypes.POINTER(_abi.CTimelineOut), ctypes.POINTER(_abi.CAuditOut),
+                    ctypes.POINTER(_abi.CAuditReport), ctypes.POINTER(_abi.CTimelineReport)]
+            L.bftsim_timeline_trace.argtypes = L.bftsim_audit_trace.argtypes[:9] + tail
+            L.bftsim_timeline_last_trace.argtypes = L.bftsim_audit_last_trace.argtypes[:4] + tail
+            L.bftsim_timeline_last_ms.argtypes = [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_float)] * 4
         L.bftsim_set_ledger_votes.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
         L.bftsim_verify_ledger.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
                                            ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(_abi.CLedgerOut),
@@ -527,6 +534,51 @@ class Simulator:
         (bftsim_accuse_last_ms)."""
         v = [ctypes.c_float() for _ in range(4)]
         _check(self.h, lib().bftsim_accuse_last_ms(self.h, *[ctypes.byref(x) for x in v]), "bftsim_accuse_last_ms")
+        return tuple(x.value for x in v)
+
+    def timeline_trace(self, trace, max_heights: int = None, key_cap: int = 0, tl_cap: int = 0):
+        """The chronicler (include/bftsim.h bftsim_timeline_trace, SPEC.md §11h) over a bftsim.trace.Trace, or anything
+        with its stream / frame_off / inst_frame0: per height the first prepare certificate, the round-change quorums and
+        the verdicts that join them to the observer's commit certificate, tallied on the device over the Prepare and
+        RoundChange frames the observer accepts. -> bftsim.trace.Timeline (its .audit: the observer's outputs of the
+        same call)"""
+        from .trace import Audit, Timeline
+        H = self.cfg.heights if max_heights is None else max_heights
+        stream = np.ascontiguousarray(trace.stream, np.uint8)
+        off = np.ascontiguousarray(trace.frame_off, np.uint64)
+        f0 = np.ascontiguousarray(trace.inst_frame0, np.uint64)
+        frames, n = len(off) - 1, len(f0) - 1
+        ok = 0 < H <= 65535                        # the library refuses it; no buffers are sized by it here
+        o, arrs = _abi.alloc_timeline(n, H if ok else 0)
+        ao, aarrs = _abi.alloc_audit(frames, n, H if ok else 0)
+        rep, arep = _abi.CTimelineReport(), _abi.CAuditReport()
+        _check(self.h, lib().bftsim_timeline_trace(self.h, stream.ctypes.data, len(stream), off.ctypes.data, frames,
+                                                   f0.ctypes.data, n, H, key_cap, tl_cap, ctypes.byref(o), ctypes.byref(ao),
+                                                   ctypes.byref(arep), ctypes.byref(rep)), "bftsim_timeline_trace")
+        return Timeline(arrs, rep, n, H, Audit(aarrs, arep, n, H))
+
+    def timeline_last_trace(self, begin: int = 0, count: int = None, key_cap: int = 0, tl_cap: int = 0):
+        """The same over the kept trace of the last launch (after crypto_verify with set_trace_keep), instances
+        [begin, begin + count): emitted, audited and chronicled on the device (bftsim_timeline_last_trace)."""
+        from .trace import Audit, Timeline
+        if count is None:
+            count = self.n_launched - begin
+        fr, _ = self.trace_sizes()
+        if begin < 0 or count < 0 or begin + count > len(fr):
+            raise BftsimError(f"timeline_last_trace: instances [{begin}, {begin + count}) outside the last launch of {len(fr)}")
+        frames, H = int(fr[begin:begin + count].sum()), self.cfg.heights
+        o, arrs = _abi.alloc_timeline(count, H)
+        ao, aarrs = _abi.alloc_audit(frames, count, H)
+        rep, arep = _abi.CTimelineReport(), _abi.CAuditReport()
+        _check(self.h, lib().bftsim_timeline_last_trace(self.h, begin, count, key_cap, tl_cap, ctypes.byref(o),
+                                                        ctypes.byref(ao), ctypes.byref(arep), ctypes.byref(rep)),
+               "bftsim_timeline_last_trace")
+        return Timeline(arrs, rep, count, H, Audit(aarrs, arep, count, H))
+
+    def timeline_ms(self):
+        """(the observer's passes, walk, rows, copies) of the last timeline call, device ms (bftsim_timeline_last_ms)."""
+        v = [ctypes.c_float() for _ in range(4)]
+        _check(self.h, lib().bftsim_timeline_last_ms(self.h, *[ctypes.byref(x) for x in v]), "bftsim_timeline_last_ms")
         return tuple(x.value for x in v)
 
     def set_ledger_votes(self, kind: str):

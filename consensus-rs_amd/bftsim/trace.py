@@ -171,6 +171,58 @@ class Accusation:
         return trace.frame(int(r["frame_a"])), trace.frame(int(r["frame_b"]))
 
 
+TIMELINE_KEY_OVERFLOW = 1
+TIMELINE_PREPARED_FIRST, TIMELINE_CERT_UNPREPARED, TIMELINE_LOCKED_OPEN = 1, 2, 4
+ROUND_NONE = 0xffff
+
+
+class Timeline:
+    """What the chronicler made of a frame stream (SPEC.md §11h), per (instance, height): prep_round, prep_frame,
+    prep_quorums, rc_quorums, rc_max_round, rc_max_frame, rc_top_round, rc_frames, flags [n, H]; prep_digest [n, H, 32];
+    prep_voters [n, H, 4]; per instance inst_flags and open_heights [n]; report: bftsim_timeline_report as a dict; audit:
+    the observer's outputs of the same call. Rounds are clipped at 0xfffe, ROUND_NONE means none; frame indices are
+    within the instance."""
+
+    def __init__(self, arrs: dict, rep, n: int, heights: int, audit: Audit = None):
+        self.n, self.heights, self.audit = n, heights, audit
+        for k in ("prep_round", "prep_frame", "prep_quorums", "rc_quorums", "rc_max_round", "rc_max_frame", "rc_top_round",
+                  "rc_frames", "flags"):
+            setattr(self, k, arrs[k].reshape(n, heights))
+        self.prep_digest = arrs["prep_digest"].reshape(n, heights, 32)
+        self.prep_voters = arrs["prep_voters"].reshape(n, heights, 4)
+        self.inst_flags, self.open_heights = arrs["inst_flags"], arrs["open_height"]
+        self.report = {k: int(getattr(rep, k)) for k, _ in rep._fields_}
+
+    def row(self, i: int, x: int) -> dict:
+        """height x (from 1) of instance i: every row field, the digest as bytes, the voters as ascending indices, the
+        flags by name too"""
+        w = self.prep_voters[i, x - 1]
+        fl = int(self.flags[i, x - 1])
+        out = {k: int(getattr(self, k)[i, x - 1]) for k in ("prep_round", "prep_frame", "prep_quorums", "rc_quorums",
+                                                           "rc_max_round", "rc_max_frame", "rc_top_round", "rc_frames")}
+        out.update(prep_digest=self.prep_digest[i, x - 1].tobytes(), flags=fl,
+                   prep_voters=[v for v in range(256) if (int(w[v >> 6]) >> (v & 63)) & 1],
+                   prepared_first=bool(fl & TIMELINE_PREPARED_FIRST), cert_unprepared=bool(fl & TIMELINE_CERT_UNPREPARED),
+                   locked_open=bool(fl & TIMELINE_LOCKED_OPEN))
+        return out
+
+    def open_height(self, i: int) -> int:
+        """the smallest height of instance i without a commit certificate, heights + 1 if there is none"""
+        return int(self.open_heights[i])
+
+    def rounds_walked(self, i: int, x: int) -> int:
+        """how far round changes carried height x: the greatest round with a round-change quorum (clipped), 0 without"""
+        r = int(self.rc_max_round[i, x - 1])
+        return 0 if r == ROUND_NONE else r
+
+    def stalled(self, i: int) -> bool:
+        """the instance stopped at its open height with a lock standing or after a round-change quorum there"""
+        x = self.open_height(i)
+        if x > self.heights:
+            return False
+        return bool(int(self.flags[i, x - 1]) & TIMELINE_LOCKED_OPEN) or int(self.rc_quorums[i, x - 1]) > 0
+
+
 def compare(audit: Audit, result: dict, begin: int = 0) -> dict:
     """The certificates against a run's result (Simulator.run / fetch; audit instance i = result instance begin + i).
     Per instance, over the committed heights: `certified` with a certificate for the committed hash, `missing`

@@ -33,6 +33,7 @@
 #include "bft_audit.h"
 #include "bft_archive.h"
 #include "bft_accuse.h"
+#include "bft_timeline.h"
 #include "bft_ledger.h"
 
 namespace bft {
@@ -677,6 +678,7 @@ struct bftsim {
     uint32_t acc_n = 0;
     float archive_ms[4] = {0, 0, 0, 0};// the observer's passes, pick, emit + heights, copies of the last archive (SPEC.md §11e)
     float accuse_ms[4] = {0, 0, 0, 0}; // the observer's passes, walk, mark + scan + gather, copies of the last accuse (SPEC.md §11g)
+    float timeline_ms[4] = {0, 0, 0, 0};// the observer's passes, walk, rows, copies of the last timeline (SPEC.md §11h)
 };
 
 static int fail(bftsim* h, int code, const std::string& msg) {
@@ -2464,12 +2466,103 @@ static int accuse_copy(bftsim* h, AccuseCont& xc, const uint8_t* p, uint64_t fra
     rep->view_overflows = xc.counts[X::CNT_VIEW_OVERFLOWS];
     return BFTSIM_OK;
 }
+// ---- the chronicler (SPEC.md §11h): a third continuation of audit_device, run after the tally's synchronisation over
+// the records, statuses, signers and certificate rows, which it only reads. Its tables are one more piece of the pool.
+namespace {
+struct TimelineCont {
+    uint32_t tl_cap;
+    const bftsim_timeline_out* out;   // the caller's
+    bftsim_timeline_report* report;
+    uint64_t bytes, o_keys, o_nkeys, o_flags, o_open, o_pround, o_rcmax, o_rctop, o_pdig, o_pvot, o_pframe, o_pq, o_rcq,
+        o_rcmf, o_rcf, o_rflags, o_counts;
+    unsigned long long counts[bft::timeline::CNT_WORDS];
+    float ms[2];                      // walk, rows
+};
+}  // namespace
+static int timeline_layout(bftsim* h, TimelineCont& tc, uint64_t inst, uint32_t max_heights) {
+    namespace T = bft::timeline;
+    const uint64_t rows = inst * max_heights, Rx = rows ? rows : 1, Ix = inst ? inst : 1;
+    if (rows >= (1ull << 31) - 1) return fail(h, BFTSIM_ENOMEM, "bftsim_timeline: 2^31 rows or more");
+    if (tc.tl_cap == 0) tc.tl_cap = T::default_cap(max_heights);
+    if (tc.tl_cap > (1ull << 40) / sizeof(T::Key) / Ix)
+        return fail(h, BFTSIM_ENOMEM, "bftsim_timeline: tl_cap x instances above 1 TiB of key tables");
+    uint64_t bytes = 0;
+    auto sized = [&](uint64_t b) { const uint64_t o = bytes; bytes += (b + 31) & ~31ull; return o; };
+    tc.o_keys = sized(Ix * tc.tl_cap * sizeof(T::Key));
+    tc.o_nkeys = sized(Ix * 4); tc.o_flags = sized(Ix * 4); tc.o_open = sized(Ix * 4);
+    tc.o_pround = sized(Rx * 2); tc.o_rcmax = sized(Rx * 2); tc.o_rctop = sized(Rx * 2);             // preset to ROUND_NONE
+    tc.o_pdig = sized(Rx * 32); tc.o_pvot = sized(Rx * 32); tc.o_pframe = sized(Rx * 4); tc.o_pq = sized(Rx * 2);
+    tc.o_rcq = sized(Rx * 2); tc.o_rcmf = sized(Rx * 4); tc.o_rcf = sized(Rx * 4); tc.o_rflags = sized(Rx);
+    tc.o_counts = sized(T::CNT_WORDS * 8);
+    tc.bytes = bytes;
+    return BFTSIM_OK;
+}
+static int timeline_passes(bftsim* h, TimelineCont& tc, uint8_t* p, const bft::audit::Recs& r, const uint8_t* d_status,
+                           const int32_t* d_signer, const uint64_t* d_if0, uint64_t inst, uint32_t max_heights,
+                           const bft::timeline::Certs& certs, hipStream_t s) {
+    namespace T = bft::timeline;
+    const T::Rows rows{(uint16_t*)(p + tc.o_pround), p + tc.o_pdig, (uint64_t*)(p + tc.o_pvot), (uint32_t*)(p + tc.o_pframe),
+                       (uint16_t*)(p + tc.o_pq), (uint16_t*)(p + tc.o_rcq), (uint16_t*)(p + tc.o_rcmax),
+                       (uint32_t*)(p + tc.o_rcmf), (uint16_t*)(p + tc.o_rctop), (uint32_t*)(p + tc.o_rcf), p + tc.o_rflags};
+    const T::Args a{r, d_status, d_signer, d_if0, inst, h->cfg.n, tc.tl_cap, max_heights, bftsim_two_thirds_majority(h->cfg.n),
+                    certs, (T::Key*)(p + tc.o_keys), (uint32_t*)(p + tc.o_nkeys), (uint32_t*)(p + tc.o_flags),
+                    (uint32_t*)(p + tc.o_open), rows, (unsigned long long*)(p + tc.o_counts)};
+    Events ev;
+    HIPCHECK(h, ev.create(3));
+    HIPCHECK(h, hipMemsetAsync(p + tc.o_nkeys, 0, tc.o_pround - tc.o_nkeys, s));
+    HIPCHECK(h, hipMemsetAsync(p + tc.o_pround, 0xff, tc.o_pdig - tc.o_pround, s));    // ROUND_NONE
+    HIPCHECK(h, hipMemsetAsync(p + tc.o_pdig, 0, tc.bytes - tc.o_pdig, s));            // the other rows, the counters
+    HIPCHECK(h, hipEventRecord(ev[0], s));
+    HIPCHECK(h, T::launch_walk(a, s));
+    HIPCHECK(h, hipEventRecord(ev[1], s));
+    HIPCHECK(h, T::launch_rows(a, s));
+    HIPCHECK(h, hipEventRecord(ev[2], s));
+    HIPCHECK(h, hipMemcpyAsync(tc.counts, p + tc.o_counts, sizeof tc.counts, hipMemcpyDeviceToHost, s));
+    HIPCHECK(h, hipStreamSynchronize(s));
+    for (int k = 0; k < 2; ++k) HIPCHECK(h, hipEventElapsedTime(&tc.ms[k], ev[k], ev[k + 1]));
+    return BFTSIM_OK;
+}
+static int timeline_copy(bftsim* h, TimelineCont& tc, const uint8_t* p, uint64_t inst, uint32_t max_heights, hipStream_t s) {
+    namespace T = bft::timeline;
+    const uint64_t rows = inst * max_heights;
+    const bftsim_timeline_out* o = tc.out;
+    Events ev;
+    HIPCHECK(h, ev.create(2));
+    HIPCHECK(h, hipEventRecord(ev[0], s));
+    const struct { void* dst; uint64_t off, b; } back[] = {
+        {o->prep_round, tc.o_pround, rows * 2}, {o->prep_digest, tc.o_pdig, rows * 32}, {o->prep_voters, tc.o_pvot, rows * 32},
+        {o->prep_frame, tc.o_pframe, rows * 4}, {o->prep_quorums, tc.o_pq, rows * 2}, {o->rc_quorums, tc.o_rcq, rows * 2},
+        {o->rc_max_round, tc.o_rcmax, rows * 2}, {o->rc_max_frame, tc.o_rcmf, rows * 4}, {o->rc_top_round, tc.o_rctop, rows * 2},
+        {o->rc_frames, tc.o_rcf, rows * 4}, {o->flags, tc.o_rflags, rows}, {o->inst_flags, tc.o_flags, inst * 4},
+        {o->open_height, tc.o_open, inst * 4}};
+    for (const auto& k : back)
+        if (k.dst && k.b) HIPCHECK(h, hipMemcpyAsync(k.dst, p + k.off, k.b, hipMemcpyDeviceToHost, s));
+    HIPCHECK(h, hipEventRecord(ev[1], s));
+    HIPCHECK(h, hipStreamSynchronize(s));
+    float copy_ms = 0;
+    HIPCHECK(h, hipEventElapsedTime(&copy_ms, ev[0], ev[1]));
+    h->timeline_ms[0] = h->audit_ms[0] + h->audit_ms[1] + h->audit_ms[2];
+    h->timeline_ms[1] = tc.ms[0]; h->timeline_ms[2] = tc.ms[1]; h->timeline_ms[3] = h->audit_ms[3] + copy_ms;
+    bftsim_timeline_report* rep = tc.report;
+    memset(rep, 0, sizeof *rep);
+    rep->prepare_frames = tc.counts[T::CNT_PREPARE_FRAMES];
+    rep->rc_frames = tc.counts[T::CNT_RC_FRAMES];
+    rep->out_of_range = tc.counts[T::CNT_OUT_OF_RANGE];
+    rep->prepared = tc.counts[T::CNT_PREPARED];
+    rep->rc_quorums = tc.counts[T::CNT_RC_QUORUMS];
+    rep->rc_heights = tc.counts[T::CNT_RC_HEIGHTS];
+    rep->prepared_first = tc.counts[T::CNT_PREPARED_FIRST];
+    rep->cert_unprepared = tc.counts[T::CNT_CERT_UNPREPARED];
+    rep->locked_open = tc.counts[T::CNT_LOCKED_OPEN];
+    rep->key_overflows = tc.counts[T::CNT_KEY_OVERFLOWS];
+    return BFTSIM_OK;
+}
 // the passes over a device stream: frame k = d_stream[d_foff[k] - base, d_foff[k + 1] - base),
 // if0 on the host. Every temporary is freed before returning; only the caller's buffers and h->audit_ms are written.
 static int audit_device(bftsim* h, const uint8_t* d_stream, const uint64_t* d_foff, uint64_t base, uint64_t frames,
                         const uint64_t* if0, uint64_t inst, uint32_t max_heights, uint32_t key_cap,
                         const bftsim_audit_out* out, bftsim_audit_report* report, hipStream_t s, float copy_in_ms,
-                        ArchiveCont* ac = nullptr, AccuseCont* xc = nullptr) {
+                        ArchiveCont* ac = nullptr, AccuseCont* xc = nullptr, TimelineCont* tc = nullptr) {
     namespace A = bft::audit;
     SigApi& sa = sig_api();
     if (key_cap == 0) key_cap = 4u * max_heights + 64u;
@@ -2494,6 +2587,11 @@ static int audit_device(bftsim* h, const uint8_t* d_stream, const uint64_t* d_fo
     if (xc) {                                                                      // the accuser's tables
         if (int rc = accuse_layout(h, *xc, F, inst, max_heights)) return rc;
         bytes += xc->bytes;
+    }
+    const uint64_t o_timeline = bytes;
+    if (tc) {                                                                      // the chronicler's tables and rows
+        if (int rc = timeline_layout(h, *tc, inst, max_heights)) return rc;
+        bytes += tc->bytes;
     }
     DevMem pool_mem;
     if (pool_mem.alloc(bytes) != hipSuccess)
@@ -2547,6 +2645,10 @@ static int audit_device(bftsim* h, const uint8_t* d_stream, const uint64_t* d_fo
     }
     if (xc)
         if (int rc = accuse_passes(h, *xc, pool + o_accuse, F, r, d_status, d_signer, d_if0, inst, s)) return rc;
+    if (tc) {
+        const bft::timeline::Certs certs{(const uint16_t*)(pool + o_cround), pool + o_cdig, (const uint32_t*)(pool + o_cframe)};
+        if (int rc = timeline_passes(h, *tc, pool + o_timeline, r, d_status, d_signer, d_if0, inst, max_heights, certs, s)) return rc;
+    }
     if (out) {
         const struct { void* dst; uint64_t off, b; } back[] = {
             {out->frame_status, o_status, F}, {out->frame_signer, o_signer, F * 4}, {out->inst_flags, o_iflags, inst * 4},
@@ -2572,6 +2674,7 @@ static int audit_device(bftsim* h, const uint8_t* d_stream, const uint64_t* d_fo
     report->key_overflows = c[A::CNT_KEY_OVERFLOWS];
     report->recoveries = F + n_seals;
     if (xc) return accuse_copy(h, *xc, pool + o_accuse, F, inst, s);
+    if (tc) return timeline_copy(h, *tc, pool + o_timeline, inst, max_heights, s);
     return ac ? archive_copy(h, *ac, pool + o_arch, inst, max_heights, s) : BFTSIM_OK;
 }
 static int audit_dims(bftsim* h, uint64_t frames, uint64_t inst, uint32_t max_heights, const char* what) {
@@ -2585,7 +2688,7 @@ static int audit_dims(bftsim* h, uint64_t frames, uint64_t inst, uint32_t max_he
 static int audit_host_stream(bftsim* h, const uint8_t* stream, uint64_t stream_bytes, const uint64_t* frame_off, uint64_t frames,
                              const uint64_t* inst_frame0, uint64_t inst_count, uint32_t max_heights, uint32_t key_cap,
                              const bftsim_audit_out* out, bftsim_audit_report* report, ArchiveCont* ac,
-                             AccuseCont* xc = nullptr) {
+                             AccuseCont* xc = nullptr, TimelineCont* tc = nullptr) {
     if (!frame_off || !inst_frame0 || (stream_bytes && !stream))
         return fail(h, BFTSIM_EINVAL, "bftsim_audit_trace: null stream, frame_off or inst_frame0");
     if (int rc = audit_dims(h, frames, inst_count, max_heights, "bftsim_audit_trace")) return rc;
@@ -2614,7 +2717,7 @@ static int audit_host_stream(bftsim* h, const uint8_t* stream, uint64_t stream_b
     HIPCHECK(h, hipStreamSynchronize(s));
     HIPCHECK(h, hipEventElapsedTime(&copy_ms, ev[0], ev[1]));
     return audit_device(h, d_in, (const uint64_t*)(d_in + sb + 16), 0, frames, inst_frame0, inst_count, max_heights, key_cap,
-                        out, report, s, copy_ms, ac, xc);
+                        out, report, s, copy_ms, ac, xc, tc);
 }
 int bftsim_audit_trace(bftsim_t* h, const uint8_t* stream, uint64_t stream_bytes, const uint64_t* frame_off, uint64_t frames,
                        const uint64_t* inst_frame0, uint64_t inst_count, uint32_t max_heights, uint32_t key_cap,
@@ -2627,7 +2730,7 @@ int bftsim_audit_trace(bftsim_t* h, const uint8_t* stream, uint64_t stream_bytes
 // the observer over the kept trace of the last launch; ac as above
 static int audit_kept_trace(bftsim* h, uint64_t inst_begin, uint64_t inst_count, uint32_t key_cap,
                             const bftsim_audit_out* out, bftsim_audit_report* report, ArchiveCont* ac,
-                            AccuseCont* xc = nullptr) {
+                            AccuseCont* xc = nullptr, TimelineCont* tc = nullptr) {
     if (int rc = trace_ready(h, "bftsim_audit_last_trace")) return rc;
     const uint64_t n = h->trace_n;
     if (inst_begin > n || inst_count > n - inst_begin)
@@ -2648,7 +2751,7 @@ static int audit_kept_trace(bftsim* h, uint64_t inst_begin, uint64_t inst_count,
         return fail(h, BFTSIM_ENOMEM, "bftsim_audit_last_trace: device memory for the stream");
     if (int rc = trace_emit(h, "bftsim_audit_last_trace", m0, m1, d_out.as<uint8_t>(), nullptr, nullptr)) return rc;
     return audit_device(h, d_out.as<uint8_t>(), h->d_tfoff + m0, base, frames, if0.data(), inst_count, h->cfg.heights,
-                        key_cap, out, report, s, 0.f, ac, xc);
+                        key_cap, out, report, s, 0.f, ac, xc, tc);
 }
 int bftsim_audit_last_trace(bftsim_t* h, uint64_t inst_begin, uint64_t inst_count, uint32_t key_cap,
                             const bftsim_audit_out* out, bftsim_audit_report* report) {
@@ -2737,6 +2840,38 @@ int bftsim_accuse_last_ms(bftsim_t* h, float* audit_ms, float* walk_ms, float* c
     if (walk_ms) *walk_ms = h->accuse_ms[1];
     if (compact_ms) *compact_ms = h->accuse_ms[2];
     if (copy_ms) *copy_ms = h->accuse_ms[3];
+    return BFTSIM_OK;
+}
+
+// ---- the chronicler's entry points (SPEC.md §11h): the observer's passes and refusals, then walk and rows
+int bftsim_timeline_trace(bftsim_t* h, const uint8_t* stream, uint64_t stream_bytes, const uint64_t* frame_off, uint64_t frames,
+                          const uint64_t* inst_frame0, uint64_t inst_count, uint32_t max_heights, uint32_t key_cap,
+                          uint32_t tl_cap, const bftsim_timeline_out* out, const bftsim_audit_out* audit_out,
+                          bftsim_audit_report* audit_report, bftsim_timeline_report* report) {
+    if (!h || !report) return BFTSIM_EINVAL;
+    if (!out) return fail(h, BFTSIM_EINVAL, "bftsim_timeline_trace: null out");
+    TimelineCont tc{};
+    tc.tl_cap = tl_cap; tc.out = out; tc.report = report;
+    bftsim_audit_report own;
+    return audit_host_stream(h, stream, stream_bytes, frame_off, frames, inst_frame0, inst_count, max_heights, key_cap,
+                             audit_out, audit_report ? audit_report : &own, nullptr, nullptr, &tc);
+}
+int bftsim_timeline_last_trace(bftsim_t* h, uint64_t inst_begin, uint64_t inst_count, uint32_t key_cap, uint32_t tl_cap,
+                               const bftsim_timeline_out* out, const bftsim_audit_out* audit_out,
+                               bftsim_audit_report* audit_report, bftsim_timeline_report* report) {
+    if (!h || !report) return BFTSIM_EINVAL;
+    if (!out) return fail(h, BFTSIM_EINVAL, "bftsim_timeline_last_trace: null out");
+    TimelineCont tc{};
+    tc.tl_cap = tl_cap; tc.out = out; tc.report = report;
+    bftsim_audit_report own;
+    return audit_kept_trace(h, inst_begin, inst_count, key_cap, audit_out, audit_report ? audit_report : &own, nullptr, nullptr, &tc);
+}
+int bftsim_timeline_last_ms(bftsim_t* h, float* audit_ms, float* walk_ms, float* rows_ms, float* copy_ms) {
+    if (!h) return BFTSIM_EINVAL;
+    if (audit_ms) *audit_ms = h->timeline_ms[0];
+    if (walk_ms) *walk_ms = h->timeline_ms[1];
+    if (rows_ms) *rows_ms = h->timeline_ms[2];
+    if (copy_ms) *copy_ms = h->timeline_ms[3];
     return BFTSIM_OK;
 }
 

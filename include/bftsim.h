@@ -451,6 +451,76 @@ int bftsim_accuse_last_trace(bftsim_t *h, uint64_t inst_begin, uint64_t inst_cou
  * them */
 int bftsim_accuse_last_ms(bftsim_t *h, float *audit_ms, float *walk_ms, float *compact_ms, float *copy_ms);
 
+/* the chronicler (SPEC.md §11h): how a height got to its certificate, or where an instance stopped. The observer's
+ * passes, then per instance over the frames it accepts (status OK or SEAL_FOREIGN) that are a Prepare or a RoundChange
+ * at a height in 1..max_heights: a Prepare votes in the key (height, round, digest), a RoundChange in the key
+ * (height, round) whatever digest it carries (round_change.rs:78-92 never reads it), the round as the full u64, a
+ * signer once per key. A key has a quorum when its distinct voters exceed bftsim_two_thirds_majority(n). Per
+ * (instance, height) the first Prepare key to reach one is described as it stood at the completing frame, the others
+ * are counted, and three flags join the row to the observer's certificate row of the same call. Rounds in the rows
+ * are clipped as cert_round is (above 0xfffe: 0xfffe; 0xffff: none); frame indices are within the instance. */
+#define BFTSIM_TIMELINE_KEY_OVERFLOW 1u   /* instance flag: a frame's key was absent from a full table: the frame was
+                                             ignored */
+#define BFTSIM_TIMELINE_PREPARED_FIRST 1u /* row flag: the height has a commit certificate, and a Prepare key with its
+                                             digest and the full round of the frame cert_frame reached its quorum at a
+                                             frame below cert_frame */
+#define BFTSIM_TIMELINE_CERT_UNPREPARED 2u /* row flag: the height has a commit certificate, and no Prepare key with its
+                                              digest, at any round, reaches a quorum in the instance (prepare.rs:59) */
+#define BFTSIM_TIMELINE_LOCKED_OPEN 4u    /* row flag: a prepare quorum and no commit certificate */
+struct bftsim_timeline_report {
+    uint64_t prepare_frames;        /* accepted Prepares with a height in range, those ignored for a full table too */
+    uint64_t rc_frames;             /* accepted RoundChanges with a height in range, those ignored for a full table
+                                       too: it exceeds the sum of bftsim_timeline_out.rc_frames, which counts only
+                                       the tallied ones, by the RoundChanges that BFTSIM_TIMELINE_KEY_OVERFLOW ignored */
+    uint64_t out_of_range;          /* accepted Prepares and RoundChanges at height 0 or above max_heights */
+    uint64_t prepared;              /* rows with a prepare quorum */
+    uint64_t rc_quorums;            /* RoundChange keys that reached a quorum */
+    uint64_t rc_heights;            /* rows with at least one of them */
+    uint64_t prepared_first;        /* rows with BFTSIM_TIMELINE_PREPARED_FIRST */
+    uint64_t cert_unprepared;       /* rows with BFTSIM_TIMELINE_CERT_UNPREPARED */
+    uint64_t locked_open;           /* rows with BFTSIM_TIMELINE_LOCKED_OPEN */
+    uint64_t key_overflows;         /* instances with BFTSIM_TIMELINE_KEY_OVERFLOW */
+};
+typedef struct bftsim_timeline_report bftsim_timeline_report;
+struct bftsim_timeline_out {        /* host, caller-owned, any pointer may be NULL; rows = inst_count * max_heights,
+                                       row inst * max_heights + height - 1 */
+    uint16_t *prep_round;           /* [rows] the round of the first Prepare key to reach a quorum, 0xffff: none */
+    uint8_t *prep_digest;           /* [rows * 32] its digest */
+    uint64_t *prep_voters;          /* [rows * 4] its voters at the completing frame */
+    uint32_t *prep_frame;           /* [rows] the completing frame (0 without a quorum) */
+    uint16_t *prep_quorums;         /* [rows] Prepare keys of the height that reached a quorum, saturating */
+    uint16_t *rc_quorums;           /* [rows] RoundChange keys of the height that reached a quorum, saturating */
+    uint16_t *rc_max_round;         /* [rows] the greatest round among them, 0xffff: none */
+    uint32_t *rc_max_frame;         /* [rows] the frame that completed that key's quorum (0 without one) */
+    uint16_t *rc_top_round;         /* [rows] the greatest round a tallied RoundChange of the height names, 0xffff: none */
+    uint32_t *rc_frames;            /* [rows] the tallied RoundChanges of the height */
+    uint8_t *flags;                 /* [rows] BFTSIM_TIMELINE_PREPARED_FIRST | _CERT_UNPREPARED | _LOCKED_OPEN */
+    uint32_t *inst_flags;           /* [inst_count] BFTSIM_TIMELINE_KEY_OVERFLOW */
+    uint32_t *open_height;          /* [inst_count] the smallest height without a commit certificate, max_heights + 1
+                                       if every height has one */
+};
+typedef struct bftsim_timeline_out bftsim_timeline_out;
+/* stream .. key_cap, audit_out and audit_report (both nullable): as bftsim_audit_trace, whose refusals are this call's
+ * and whose outputs those two receive unchanged. tl_cap: keys per instance's table (0 = 4 * max_heights + 64); nothing
+ * is evicted. Every counted frame is matched against all keys its instance holds so far, as the observer's are under
+ * key_cap: a stream with many distinct (height, round) pairs costs frames x min(keys, tl_cap) comparisons per instance,
+ * so tl_cap is also the bound on what a hostile stream can make the walk cost; raise it only for streams whose rounds
+ * are known to run that far. BFTSIM_EINVAL too for a null out or report; BFTSIM_ENOMEM, before anything is launched, for tables the
+ * device cannot hold. A refused call writes nothing; hostile frame contents are never an error; the handle's run state
+ * is untouched; no secrets are needed. */
+int bftsim_timeline_trace(bftsim_t *h, const uint8_t *stream, uint64_t stream_bytes, const uint64_t *frame_off, uint64_t frames,
+                          const uint64_t *inst_frame0, uint64_t inst_count, uint32_t max_heights, uint32_t key_cap,
+                          uint32_t tl_cap, const bftsim_timeline_out *out, const bftsim_audit_out *audit_out,
+                          bftsim_audit_report *audit_report, bftsim_timeline_report *report);
+/* the same over the kept trace of the last launch, as bftsim_audit_last_trace: the stream never leaves the device */
+int bftsim_timeline_last_trace(bftsim_t *h, uint64_t inst_begin, uint64_t inst_count, uint32_t key_cap, uint32_t tl_cap,
+                               const bftsim_timeline_out *out, const bftsim_audit_out *audit_out,
+                               bftsim_audit_report *audit_report, bftsim_timeline_report *report);
+/* diagnostics: device times (ms, HIP events) of the last timeline call: the observer's passes (decode, recoveries,
+ * classification + tally), the walk kernel, the rows kernel, and the copies, as scripts/timeline_bench.py records
+ * them */
+int bftsim_timeline_last_ms(bftsim_t *h, float *audit_ms, float *walk_ms, float *rows_ms, float *copy_ms);
+
 /* the importer (SPEC.md §11d): what a syncing node runs on every Header it is handed, Engine::verify_header with
  * seal = true and verify_seal (src/consensus/backend.rs:319-367), batched: every header of every instance's ledger,
  * verified from untrusted bytes on the device.
