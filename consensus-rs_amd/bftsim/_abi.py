@@ -128,6 +128,41 @@ def alloc_timeline(n_inst: int, heights: int):
     return o, arrs
 
 
+class CRollCallReport(ctypes.Structure):
+    _fields_ = [("frames", ctypes.c_uint64), ("out_of_range", ctypes.c_uint64), ("views", ctypes.c_uint64),
+                ("by_outcome", ctypes.c_uint64 * 3)] + [(k, ctypes.c_uint64) for k in (
+                    "won", "silent", "silent_instances", "partial_instances")]
+
+
+# bftsim_rollcall_out: the rows' fields -> words per (instance, validator) row, all uint32; then the instances' fields
+ROLLCALL_ROWS = dict(frames=4, last_height=1, last_frame=1, due=1, proposed=1, missed=1, won=1)
+ROLLCALL_INST = ("inst_views", "inst_silent", "inst_flags")
+
+
+class CRollCallOut(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in tuple(ROLLCALL_ROWS) + ROLLCALL_INST + ("records",)] + [
+        ("rec_cap", ctypes.c_uint64)]
+
+
+# bftsim_rollcall_record
+ROLLCALL_RECORD = np.dtype([("round", "<u8"), ("inst", "<u4"), ("height", "<u4"), ("proposer", "<u4"), ("outcome", "<u4"),
+                            ("start_frame", "<u4"), ("pp_frame", "<u4")])
+
+
+def alloc_rollcall(n_inst: int, n: int, rec_cap: int):
+    """host buffers of bftsim_rollcall_out -> (struct, arrays)"""
+    rows = n_inst * n
+    arrs = {k: np.zeros(rows * w, np.uint32) for k, w in ROLLCALL_ROWS.items()}
+    arrs["last_frame"][:] = 0xffffffff
+    arrs.update(inst_views=np.zeros(n_inst, np.uint32), inst_silent=np.zeros(n_inst * 4, np.uint64),
+                inst_flags=np.zeros(n_inst, np.uint32), records=np.empty(rec_cap, ROLLCALL_RECORD))
+    o = CRollCallOut()
+    for k, a in arrs.items():
+        setattr(o, k, a.ctypes.data if a.size else None)
+    o.rec_cap = rec_cap
+    return o, arrs
+
+
 def alloc_archive(n_inst: int, heights: int, slot_bytes: int):
     """host buffers of bftsim_archive_trace: the header slots, their lengths and bftsim_archive_out -> (hdr, hdr_len,
     struct, arrays)"""

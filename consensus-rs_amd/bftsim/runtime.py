@@ -97,6 +97,14 @@ def lib():
             L.bftsim_timeline_trace.argtypes = L.bftsim_audit_trace.argtypes[:9] + tail
             L.bftsim_timeline_last_trace.argtypes = L.bftsim_audit_last_trace.argtypes[:4] + tail
             L.bftsim_timeline_last_ms.argtypes = [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_float)] * 4
+        if not os.environ.get("BFTSIM_LIB") or hasattr(L, "bftsim_rollcall_trace"):
+            # (an A/B build of an earlier commit may lack them, scripts/rollcall_bench.py --parent-lib; the product must not)
+            tail = [ctypes.c_uint32, ctypes.POINTER(_abi.CRollCallOut), ctypes.POINTER(_abi.CRollCallReport),
+                    ctypes.POINTER(_abi.CAuditOut), ctypes.POINTER(_abi.CAuditReport),
+                    ctypes.POINTER(_abi.CTimelineOut), ctypes.POINTER(_abi.CTimelineReport)]
+            L.bftsim_rollcall_trace.argtypes = L.bftsim_audit_trace.argtypes[:9] + tail
+            L.bftsim_rollcall_last_trace.argtypes = L.bftsim_audit_last_trace.argtypes[:4] + tail
+            L.bftsim_rollcall_last_ms.argtypes = [ctypes.c_void_p] + [ctypes.POINTER(ctypes.c_float)] * 6
         L.bftsim_set_ledger_votes.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
         L.bftsim_verify_ledger.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p,
                                            ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(_abi.CLedgerOut),
@@ -579,6 +587,55 @@ class Simulator:
         """(the observer's passes, walk, rows, copies) of the last timeline call, device ms (bftsim_timeline_last_ms)."""
         v = [ctypes.c_float() for _ in range(4)]
         _check(self.h, lib().bftsim_timeline_last_ms(self.h, *[ctypes.byref(x) for x in v]), "bftsim_timeline_last_ms")
+        return tuple(x.value for x in v)
+
+    def _rollcall_result(self, call, what, frames, n, H, rec_cap, tl_cap):
+        from .trace import Audit, RollCall, Timeline
+        if self.cfg.n > 256:
+            raise BftsimError(f"{what}: more than 256 validators")
+        cap = tl_cap or 4 * H + 64
+        o, arrs = _abi.alloc_rollcall(n, self.cfg.n, n * (H + cap) if rec_cap is None else rec_cap)
+        ao, aarrs = _abi.alloc_audit(frames, n, H)
+        to, tarrs = _abi.alloc_timeline(n, H)
+        rep, arep, trep = _abi.CRollCallReport(), _abi.CAuditReport(), _abi.CTimelineReport()
+        _check(self.h, call(ctypes.byref(o), ctypes.byref(rep), ctypes.byref(ao), ctypes.byref(arep), ctypes.byref(to),
+                            ctypes.byref(trep)), what)
+        audit = Audit(aarrs, arep, n, H)
+        return RollCall(arrs, rep, n, self.cfg.n, audit, Timeline(tarrs, trep, n, H, audit))
+
+    def rollcall_trace(self, trace, max_heights: int = None, key_cap: int = 0, tl_cap: int = 0, rec_cap: int = None):
+        """The roll call (include/bftsim.h bftsim_rollcall_trace, SPEC.md §11i) over a bftsim.trace.Trace, or anything
+        with its stream / frame_off / inst_frame0: per validator what it signed, and per view the wire proves started
+        its proposer and whether that proposer's PrePrepare is there, found on the device behind the observer and the
+        chronicler. rec_cap: every possible view by default (the pages of an np.empty cost nothing until written).
+        -> bftsim.trace.RollCall (its .audit and .timeline: their outputs of the same call)"""
+        H = self.cfg.heights if max_heights is None else max_heights
+        stream = np.ascontiguousarray(trace.stream, np.uint8)
+        off = np.ascontiguousarray(trace.frame_off, np.uint64)
+        f0 = np.ascontiguousarray(trace.inst_frame0, np.uint64)
+        frames, n = len(off) - 1, len(f0) - 1
+        ok = 0 < H <= 65535                        # the library refuses it; no buffers are sized by it here
+        call = lambda *tail: lib().bftsim_rollcall_trace(self.h, stream.ctypes.data, len(stream), off.ctypes.data, frames,
+                                                         f0.ctypes.data, n, H, key_cap, tl_cap, *tail)
+        return self._rollcall_result(call, "bftsim_rollcall_trace", frames, n, H if ok else 0, rec_cap, tl_cap)
+
+    def rollcall_last_trace(self, begin: int = 0, count: int = None, key_cap: int = 0, tl_cap: int = 0, rec_cap: int = None):
+        """The same over the kept trace of the last launch (after crypto_verify with set_trace_keep), instances
+        [begin, begin + count): emitted, audited, chronicled and called on the device (bftsim_rollcall_last_trace)."""
+        if count is None:
+            count = self.n_launched - begin
+        fr, _ = self.trace_sizes()
+        if begin < 0 or count < 0 or begin + count > len(fr):
+            raise BftsimError(f"rollcall_last_trace: instances [{begin}, {begin + count}) outside the last launch of {len(fr)}")
+        frames = int(fr[begin:begin + count].sum())
+        call = lambda *tail: lib().bftsim_rollcall_last_trace(self.h, begin, count, key_cap, tl_cap, *tail)
+        return self._rollcall_result(call, "bftsim_rollcall_last_trace", frames, count, self.cfg.heights, rec_cap, tl_cap)
+
+    def rollcall_ms(self):
+        """(the observer's passes, the chronicler's walk + rows, views, walk, scan + gather, copies) of the last roll
+        call, device ms (bftsim_rollcall_last_ms)."""
+        v = [ctypes.c_float() for _ in range(6)]
+        _check(self.h, lib().bftsim_rollcall_last_ms(self.h, *[ctypes.byref(x) for x in v]), "bftsim_rollcall_last_ms")
         return tuple(x.value for x in v)
 
     def set_ledger_votes(self, kind: str):

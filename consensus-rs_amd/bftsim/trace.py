@@ -223,6 +223,52 @@ class Timeline:
         return bool(int(self.flags[i, x - 1]) & TIMELINE_LOCKED_OPEN) or int(self.rc_quorums[i, x - 1]) > 0
 
 
+ROLLCALL_PROPOSED, ROLLCALL_MISSED, ROLLCALL_UNATTRIBUTED, ROLLCALL_WON = 1, 2, 3, 0x100
+ROLLCALL_PARTIAL = 1
+ROLLCALL_NONE = 0xffffffff
+
+
+class RollCall:
+    """What the roll call made of a frame stream (SPEC.md §11i). Per (instance, validator): frames [n, N, 4] (the counting
+    frames it signed, by code 1..4), last_height, last_frame, due, proposed, won [n, N] (these, and the missed counts
+    beside the method missed(i), also in the dict `arrays`); per instance inst_views,
+    inst_flags [n] and inst_silent [n, 4]; records, a structured array (round, inst, height, proposer, outcome,
+    start_frame, pp_frame), one per due view, instance-major and by (height, round) within an instance; report:
+    bftsim_rollcall_report as a dict (views: all that were found, also when rec_cap kept fewer); audit and timeline: the
+    observer's and the chronicler's outputs of the same call. Frame indices are within the instance."""
+
+    def __init__(self, arrs: dict, rep, n: int, validators: int, audit: Audit = None, timeline: Timeline = None):
+        self.n, self.validators, self.audit, self.timeline = n, validators, audit, timeline
+        self.arrays = {k: arrs[k].reshape(n, validators) for k in ("last_height", "last_frame", "due", "proposed", "missed", "won")}
+        self.arrays.update(frames=arrs["frames"].reshape(n, validators, 4), inst_views=arrs["inst_views"],
+                           inst_silent=arrs["inst_silent"].reshape(n, 4), inst_flags=arrs["inst_flags"])
+        for k, a in self.arrays.items():
+            if k != "missed":                      # missed(i) is the method; the counts are arrays["missed"]
+                setattr(self, k, a)
+        self.report = {k: (list(getattr(rep, k)) if k == "by_outcome" else int(getattr(rep, k))) for k, _ in rep._fields_}
+        self.records = arrs["records"][:min(self.report["views"], len(arrs["records"]))]
+
+    def row(self, i: int, v: int) -> dict:
+        """validator v of instance i: every row field, frames as the list by code"""
+        out = {k: int(self.arrays[k][i, v]) for k in ("last_height", "last_frame", "due", "proposed", "missed", "won")}
+        out["frames"] = [int(x) for x in self.frames[i, v]]
+        return out
+
+    def views(self, i: int):
+        """the records of instance i among those the call returned, by (height, round) ascending"""
+        return self.records[self.records["inst"] == i]
+
+    def missed(self, i: int) -> list:
+        """[(height, round, proposer)] of the views of instance i whose proposer sent no PrePrepare"""
+        return [(int(r["height"]), int(r["round"]), int(r["proposer"])) for r in self.views(i)
+                if int(r["outcome"]) == ROLLCALL_MISSED]
+
+    def silent(self, i: int) -> list:
+        """validator indices without a counting frame in instance i, ascending"""
+        w = self.inst_silent[i]
+        return [v for v in range(256) if (int(w[v >> 6]) >> (v & 63)) & 1]
+
+
 def compare(audit: Audit, result: dict, begin: int = 0) -> dict:
     """The certificates against a run's result (Simulator.run / fetch; audit instance i = result instance begin + i).
     Per instance, over the committed heights: `certified` with a certificate for the committed hash, `missing`

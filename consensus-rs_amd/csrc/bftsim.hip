@@ -34,6 +34,7 @@
 #include "bft_archive.h"
 #include "bft_accuse.h"
 #include "bft_timeline.h"
+#include "bft_rollcall.h"
 #include "bft_ledger.h"
 
 namespace bft {
@@ -679,6 +680,7 @@ struct bftsim {
     float archive_ms[4] = {0, 0, 0, 0};// the observer's passes, pick, emit + heights, copies of the last archive (SPEC.md §11e)
     float accuse_ms[4] = {0, 0, 0, 0}; // the observer's passes, walk, mark + scan + gather, copies of the last accuse (SPEC.md §11g)
     float timeline_ms[4] = {0, 0, 0, 0};// the observer's passes, walk, rows, copies of the last timeline (SPEC.md §11h)
+    float rollcall_ms[6] = {0, 0, 0, 0, 0, 0};   // the observer's, the chronicler's, views, walk, scan + gather, copies (§11i)
 };
 
 static int fail(bftsim* h, int code, const std::string& msg) {
@@ -2557,12 +2559,127 @@ static int timeline_copy(bftsim* h, TimelineCont& tc, const uint8_t* p, uint64_t
     rep->key_overflows = tc.counts[T::CNT_KEY_OVERFLOWS];
     return BFTSIM_OK;
 }
+// ---- the roll call (SPEC.md §11i): a fourth continuation of audit_device. It lays out and runs the chronicler's piece
+// (timeline_layout, timeline_passes) and then its own passes over the chronicler's key tables, which it only reads.
+namespace {
+struct RollCont {
+    TimelineCont tc;                  // out and report: the caller's, or stand-ins
+    const bftsim_rollcall_out* out;   // the caller's
+    bftsim_rollcall_report* report;
+    uint64_t rec_cap, bytes, o_tl, o_views, o_nviews, o_pos, o_frames, o_lh, o_lf, o_due, o_prop, o_miss, o_won, o_silent,
+        o_flags, o_recs, o_counts, o_scan;
+    size_t scan_bytes;
+    unsigned long long counts[bft::rollcall::CNT_WORDS];
+    uint32_t total;                   // the scan's
+    float ms[3];                      // views, walk, scan + gather
+};
+}  // namespace
+static int rollcall_layout(bftsim* h, RollCont& rc, uint64_t inst, uint32_t max_heights) {
+    namespace R = bft::rollcall;
+    if (int e = timeline_layout(h, rc.tc, inst, max_heights)) return e;
+    const uint64_t Ix = inst ? inst : 1, rows = inst * h->cfg.n, Rx = rows ? rows : 1;
+    const uint64_t vcap = R::view_cap(max_heights, rc.tc.tl_cap);
+    if (rows >= (1ull << 31) - 1) return fail(h, BFTSIM_ENOMEM, "bftsim_rollcall: 2^31 rows or more");
+    if (vcap > (1ull << 40) / sizeof(R::View) / Ix)
+        return fail(h, BFTSIM_ENOMEM, "bftsim_rollcall: views x instances above 1 TiB of view tables");
+    const uint64_t most = Ix * vcap;                                               // every view of the call
+    rc.rec_cap = rc.out->records ? (rc.out->rec_cap < most ? rc.out->rec_cap : most) : 0;
+    uint64_t bytes = rc.tc.bytes;
+    auto sized = [&](uint64_t b) { const uint64_t o = bytes; bytes += (b + 31) & ~31ull; return o; };
+    rc.o_tl = 0;
+    rc.o_views = sized(most * sizeof(R::View));
+    rc.o_nviews = sized((inst + 1) * 4); rc.o_pos = sized((inst + 1) * 4);
+    rc.o_frames = sized(Rx * 16); rc.o_lh = sized(Rx * 4); rc.o_lf = sized(Rx * 4); rc.o_due = sized(Rx * 4);
+    rc.o_prop = sized(Rx * 4); rc.o_miss = sized(Rx * 4); rc.o_won = sized(Rx * 4);
+    rc.o_silent = sized(Ix * 32); rc.o_flags = sized(Ix * 4);
+    rc.o_recs = sized((rc.rec_cap ? rc.rec_cap : 1) * sizeof(R::Record));
+    rc.o_counts = sized(R::CNT_WORDS * 8);
+    rc.scan_bytes = 0;
+    HIPCHECK(h, hipcub::DeviceScan::ExclusiveSum(nullptr, rc.scan_bytes, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)(inst + 1)));
+    rc.o_scan = sized(rc.scan_bytes ? rc.scan_bytes : 1);
+    rc.bytes = bytes;
+    return BFTSIM_OK;
+}
+static int rollcall_passes(bftsim* h, RollCont& rc, uint8_t* p, const bft::audit::Recs& r, const uint8_t* d_status,
+                           const int32_t* d_signer, const uint64_t* d_if0, uint64_t inst, uint32_t max_heights,
+                           const bft::timeline::Certs& certs, hipStream_t s) {
+    namespace R = bft::rollcall;
+    if (int e = timeline_passes(h, rc.tc, p + rc.o_tl, r, d_status, d_signer, d_if0, inst, max_heights, certs, s)) return e;
+    const R::Rows rows{(uint32_t*)(p + rc.o_frames), (uint32_t*)(p + rc.o_lh), (uint32_t*)(p + rc.o_lf), (uint32_t*)(p + rc.o_due),
+                       (uint32_t*)(p + rc.o_prop), (uint32_t*)(p + rc.o_miss), (uint32_t*)(p + rc.o_won)};
+    const R::Args a{r, d_status, d_signer, d_if0, inst, h->cfg.n, rc.tc.tl_cap, max_heights,
+                    h->cfg.seed_byte_order == BFTSIM_SEED_LE ? 1u : 0u, h->d_ghash, certs,
+                    (const bft::timeline::Key*)(p + rc.o_tl + rc.tc.o_keys), (const uint32_t*)(p + rc.o_tl + rc.tc.o_nkeys),
+                    (const uint32_t*)(p + rc.o_tl + rc.tc.o_flags), (R::View*)(p + rc.o_views), (uint32_t*)(p + rc.o_nviews),
+                    (uint32_t*)(p + rc.o_pos), rows, (uint64_t*)(p + rc.o_silent), (uint32_t*)(p + rc.o_flags),
+                    (R::Record*)(p + rc.o_recs), rc.rec_cap, (unsigned long long*)(p + rc.o_counts)};
+    Events ev;
+    HIPCHECK(h, ev.create(4));
+    HIPCHECK(h, hipMemsetAsync(p + rc.o_nviews, 0, rc.o_recs - rc.o_nviews, s));      // instances without a wave, the bitmaps' tails
+    HIPCHECK(h, hipMemsetAsync(p + rc.o_counts, 0, R::CNT_WORDS * 8, s));
+    HIPCHECK(h, hipEventRecord(ev[0], s));
+    HIPCHECK(h, R::launch_views(a, s));
+    HIPCHECK(h, hipEventRecord(ev[1], s));
+    HIPCHECK(h, R::launch_walk(a, s));
+    HIPCHECK(h, hipEventRecord(ev[2], s));
+    HIPCHECK(h, hipcub::DeviceScan::ExclusiveSum(p + rc.o_scan, rc.scan_bytes, a.inst_views, a.pos, (int)(inst + 1), s));
+    HIPCHECK(h, R::launch_gather(a, s));
+    HIPCHECK(h, hipEventRecord(ev[3], s));
+    HIPCHECK(h, hipMemcpyAsync(rc.counts, p + rc.o_counts, sizeof rc.counts, hipMemcpyDeviceToHost, s));
+    HIPCHECK(h, hipMemcpyAsync(&rc.total, a.pos + inst, 4, hipMemcpyDeviceToHost, s));
+    HIPCHECK(h, hipStreamSynchronize(s));
+    for (int k = 0; k < 3; ++k) HIPCHECK(h, hipEventElapsedTime(&rc.ms[k], ev[k], ev[k + 1]));
+    if (rc.total != rc.counts[R::CNT_VIEWS])
+        return fail(h, BFTSIM_EHIP, "bftsim_rollcall: the scan's total disagrees with the walk's count");
+    return BFTSIM_OK;
+}
+static int rollcall_copy(bftsim* h, RollCont& rc, const uint8_t* p, uint64_t inst, uint32_t max_heights, hipStream_t s) {
+    namespace R = bft::rollcall;
+    float kept[4];                                                 // bftsim_timeline_last_ms speaks of the last timeline call
+    memcpy(kept, h->timeline_ms, sizeof kept);
+    const int e = timeline_copy(h, rc.tc, p + rc.o_tl, inst, max_heights, s);
+    const float tl_ms = h->timeline_ms[1] + h->timeline_ms[2], tl_copy = h->timeline_ms[3];
+    memcpy(h->timeline_ms, kept, sizeof kept);
+    if (e) return e;
+    const uint64_t rows = inst * h->cfg.n, written = rc.total < rc.rec_cap ? rc.total : rc.rec_cap;
+    const bftsim_rollcall_out* o = rc.out;
+    Events ev;
+    HIPCHECK(h, ev.create(2));
+    HIPCHECK(h, hipEventRecord(ev[0], s));
+    const struct { void* dst; uint64_t off, b; } back[] = {
+        {o->frames, rc.o_frames, rows * 16}, {o->last_height, rc.o_lh, rows * 4}, {o->last_frame, rc.o_lf, rows * 4},
+        {o->due, rc.o_due, rows * 4}, {o->proposed, rc.o_prop, rows * 4}, {o->missed, rc.o_miss, rows * 4},
+        {o->won, rc.o_won, rows * 4}, {o->inst_views, rc.o_nviews, inst * 4}, {o->inst_silent, rc.o_silent, inst * 32},
+        {o->inst_flags, rc.o_flags, inst * 4}, {o->records, rc.o_recs, written * sizeof(R::Record)}};
+    for (const auto& k : back)
+        if (k.dst && k.b) HIPCHECK(h, hipMemcpyAsync(k.dst, p + k.off, k.b, hipMemcpyDeviceToHost, s));
+    HIPCHECK(h, hipEventRecord(ev[1], s));
+    HIPCHECK(h, hipStreamSynchronize(s));
+    float copy_ms = 0;
+    HIPCHECK(h, hipEventElapsedTime(&copy_ms, ev[0], ev[1]));
+    h->rollcall_ms[0] = h->audit_ms[0] + h->audit_ms[1] + h->audit_ms[2];
+    h->rollcall_ms[1] = tl_ms;
+    for (int k = 0; k < 3; ++k) h->rollcall_ms[2 + k] = rc.ms[k];
+    h->rollcall_ms[5] = tl_copy + copy_ms;
+    bftsim_rollcall_report* rep = rc.report;
+    memset(rep, 0, sizeof *rep);
+    rep->frames = rc.counts[R::CNT_FRAMES];
+    rep->out_of_range = rc.counts[R::CNT_OUT_OF_RANGE];
+    rep->views = rc.counts[R::CNT_VIEWS];
+    for (int k = 0; k < 3; ++k) rep->by_outcome[k] = rc.counts[R::CNT_OUTCOME + k];
+    rep->won = rc.counts[R::CNT_WON];
+    rep->silent = rc.counts[R::CNT_SILENT];
+    rep->silent_instances = rc.counts[R::CNT_SILENT_INST];
+    rep->partial_instances = rc.counts[R::CNT_PARTIAL_INST];
+    return BFTSIM_OK;
+}
 // the passes over a device stream: frame k = d_stream[d_foff[k] - base, d_foff[k + 1] - base),
 // if0 on the host. Every temporary is freed before returning; only the caller's buffers and h->audit_ms are written.
 static int audit_device(bftsim* h, const uint8_t* d_stream, const uint64_t* d_foff, uint64_t base, uint64_t frames,
                         const uint64_t* if0, uint64_t inst, uint32_t max_heights, uint32_t key_cap,
                         const bftsim_audit_out* out, bftsim_audit_report* report, hipStream_t s, float copy_in_ms,
-                        ArchiveCont* ac = nullptr, AccuseCont* xc = nullptr, TimelineCont* tc = nullptr) {
+                        ArchiveCont* ac = nullptr, AccuseCont* xc = nullptr, TimelineCont* tc = nullptr,
+                        RollCont* rc = nullptr) {
     namespace A = bft::audit;
     SigApi& sa = sig_api();
     if (key_cap == 0) key_cap = 4u * max_heights + 64u;
@@ -2592,6 +2709,11 @@ static int audit_device(bftsim* h, const uint8_t* d_stream, const uint64_t* d_fo
     if (tc) {                                                                      // the chronicler's tables and rows
         if (int rc = timeline_layout(h, *tc, inst, max_heights)) return rc;
         bytes += tc->bytes;
+    }
+    const uint64_t o_roll = bytes;
+    if (rc) {                                                                      // the chronicler's piece, then the roll call's
+        if (int e = rollcall_layout(h, *rc, inst, max_heights)) return e;
+        bytes += rc->bytes;
     }
     DevMem pool_mem;
     if (pool_mem.alloc(bytes) != hipSuccess)
@@ -2649,6 +2771,10 @@ static int audit_device(bftsim* h, const uint8_t* d_stream, const uint64_t* d_fo
         const bft::timeline::Certs certs{(const uint16_t*)(pool + o_cround), pool + o_cdig, (const uint32_t*)(pool + o_cframe)};
         if (int rc = timeline_passes(h, *tc, pool + o_timeline, r, d_status, d_signer, d_if0, inst, max_heights, certs, s)) return rc;
     }
+    if (rc) {
+        const bft::timeline::Certs certs{(const uint16_t*)(pool + o_cround), pool + o_cdig, (const uint32_t*)(pool + o_cframe)};
+        if (int e = rollcall_passes(h, *rc, pool + o_roll, r, d_status, d_signer, d_if0, inst, max_heights, certs, s)) return e;
+    }
     if (out) {
         const struct { void* dst; uint64_t off, b; } back[] = {
             {out->frame_status, o_status, F}, {out->frame_signer, o_signer, F * 4}, {out->inst_flags, o_iflags, inst * 4},
@@ -2675,6 +2801,7 @@ static int audit_device(bftsim* h, const uint8_t* d_stream, const uint64_t* d_fo
     report->recoveries = F + n_seals;
     if (xc) return accuse_copy(h, *xc, pool + o_accuse, F, inst, s);
     if (tc) return timeline_copy(h, *tc, pool + o_timeline, inst, max_heights, s);
+    if (rc) return rollcall_copy(h, *rc, pool + o_roll, inst, max_heights, s);
     return ac ? archive_copy(h, *ac, pool + o_arch, inst, max_heights, s) : BFTSIM_OK;
 }
 static int audit_dims(bftsim* h, uint64_t frames, uint64_t inst, uint32_t max_heights, const char* what) {
@@ -2688,7 +2815,7 @@ static int audit_dims(bftsim* h, uint64_t frames, uint64_t inst, uint32_t max_he
 static int audit_host_stream(bftsim* h, const uint8_t* stream, uint64_t stream_bytes, const uint64_t* frame_off, uint64_t frames,
                              const uint64_t* inst_frame0, uint64_t inst_count, uint32_t max_heights, uint32_t key_cap,
                              const bftsim_audit_out* out, bftsim_audit_report* report, ArchiveCont* ac,
-                             AccuseCont* xc = nullptr, TimelineCont* tc = nullptr) {
+                             AccuseCont* xc = nullptr, TimelineCont* tc = nullptr, RollCont* rc = nullptr) {
     if (!frame_off || !inst_frame0 || (stream_bytes && !stream))
         return fail(h, BFTSIM_EINVAL, "bftsim_audit_trace: null stream, frame_off or inst_frame0");
     if (int rc = audit_dims(h, frames, inst_count, max_heights, "bftsim_audit_trace")) return rc;
@@ -2717,7 +2844,7 @@ static int audit_host_stream(bftsim* h, const uint8_t* stream, uint64_t stream_b
     HIPCHECK(h, hipStreamSynchronize(s));
     HIPCHECK(h, hipEventElapsedTime(&copy_ms, ev[0], ev[1]));
     return audit_device(h, d_in, (const uint64_t*)(d_in + sb + 16), 0, frames, inst_frame0, inst_count, max_heights, key_cap,
-                        out, report, s, copy_ms, ac, xc, tc);
+                        out, report, s, copy_ms, ac, xc, tc, rc);
 }
 int bftsim_audit_trace(bftsim_t* h, const uint8_t* stream, uint64_t stream_bytes, const uint64_t* frame_off, uint64_t frames,
                        const uint64_t* inst_frame0, uint64_t inst_count, uint32_t max_heights, uint32_t key_cap,
@@ -2730,7 +2857,7 @@ int bftsim_audit_trace(bftsim_t* h, const uint8_t* stream, uint64_t stream_bytes
 // the observer over the kept trace of the last launch; ac as above
 static int audit_kept_trace(bftsim* h, uint64_t inst_begin, uint64_t inst_count, uint32_t key_cap,
                             const bftsim_audit_out* out, bftsim_audit_report* report, ArchiveCont* ac,
-                            AccuseCont* xc = nullptr, TimelineCont* tc = nullptr) {
+                            AccuseCont* xc = nullptr, TimelineCont* tc = nullptr, RollCont* rc = nullptr) {
     if (int rc = trace_ready(h, "bftsim_audit_last_trace")) return rc;
     const uint64_t n = h->trace_n;
     if (inst_begin > n || inst_count > n - inst_begin)
@@ -2751,7 +2878,7 @@ static int audit_kept_trace(bftsim* h, uint64_t inst_begin, uint64_t inst_count,
         return fail(h, BFTSIM_ENOMEM, "bftsim_audit_last_trace: device memory for the stream");
     if (int rc = trace_emit(h, "bftsim_audit_last_trace", m0, m1, d_out.as<uint8_t>(), nullptr, nullptr)) return rc;
     return audit_device(h, d_out.as<uint8_t>(), h->d_tfoff + m0, base, frames, if0.data(), inst_count, h->cfg.heights,
-                        key_cap, out, report, s, 0.f, ac, xc, tc);
+                        key_cap, out, report, s, 0.f, ac, xc, tc, rc);
 }
 int bftsim_audit_last_trace(bftsim_t* h, uint64_t inst_begin, uint64_t inst_count, uint32_t key_cap,
                             const bftsim_audit_out* out, bftsim_audit_report* report) {
@@ -2872,6 +2999,60 @@ int bftsim_timeline_last_ms(bftsim_t* h, float* audit_ms, float* walk_ms, float*
     if (walk_ms) *walk_ms = h->timeline_ms[1];
     if (rows_ms) *rows_ms = h->timeline_ms[2];
     if (copy_ms) *copy_ms = h->timeline_ms[3];
+    return BFTSIM_OK;
+}
+
+// ---- the roll call's entry points (SPEC.md §11i): the observer's passes and refusals, the chronicler's walk and rows,
+// then views, walk and gather
+namespace {
+struct RollStandIns {                 // what the chronicler's piece writes when the caller takes none of it
+    bftsim_timeline_out out;
+    bftsim_timeline_report report;
+};
+}  // namespace
+static int rollcall_args(bftsim* h, RollCont& rc, RollStandIns& own, uint32_t tl_cap, const bftsim_rollcall_out* out,
+                         bftsim_rollcall_report* report, const bftsim_timeline_out* timeline_out,
+                         bftsim_timeline_report* timeline_report, const char* what) {
+    if (!out) return fail(h, BFTSIM_EINVAL, std::string(what) + ": null out");
+    if (out->rec_cap && !out->records) return fail(h, BFTSIM_EINVAL, std::string(what) + ": rec_cap without records");
+    if (h->cfg.n > 256u) return fail(h, BFTSIM_EINVAL, std::string(what) + ": more than 256 validators");
+    memset(&own, 0, sizeof own);
+    rc.tc.tl_cap = tl_cap; rc.tc.out = timeline_out ? timeline_out : &own.out;
+    rc.tc.report = timeline_report ? timeline_report : &own.report;
+    rc.out = out; rc.report = report;
+    return BFTSIM_OK;
+}
+int bftsim_rollcall_trace(bftsim_t* h, const uint8_t* stream, uint64_t stream_bytes, const uint64_t* frame_off, uint64_t frames,
+                          const uint64_t* inst_frame0, uint64_t inst_count, uint32_t max_heights, uint32_t key_cap,
+                          uint32_t tl_cap, const bftsim_rollcall_out* out, bftsim_rollcall_report* report,
+                          const bftsim_audit_out* audit_out, bftsim_audit_report* audit_report,
+                          const bftsim_timeline_out* timeline_out, bftsim_timeline_report* timeline_report) {
+    if (!h || !report) return BFTSIM_EINVAL;
+    RollCont rc{};
+    RollStandIns own_tl;
+    if (int e = rollcall_args(h, rc, own_tl, tl_cap, out, report, timeline_out, timeline_report, "bftsim_rollcall_trace")) return e;
+    bftsim_audit_report own;
+    return audit_host_stream(h, stream, stream_bytes, frame_off, frames, inst_frame0, inst_count, max_heights, key_cap,
+                             audit_out, audit_report ? audit_report : &own, nullptr, nullptr, nullptr, &rc);
+}
+int bftsim_rollcall_last_trace(bftsim_t* h, uint64_t inst_begin, uint64_t inst_count, uint32_t key_cap, uint32_t tl_cap,
+                               const bftsim_rollcall_out* out, bftsim_rollcall_report* report,
+                               const bftsim_audit_out* audit_out, bftsim_audit_report* audit_report,
+                               const bftsim_timeline_out* timeline_out, bftsim_timeline_report* timeline_report) {
+    if (!h || !report) return BFTSIM_EINVAL;
+    RollCont rc{};
+    RollStandIns own_tl;
+    if (int e = rollcall_args(h, rc, own_tl, tl_cap, out, report, timeline_out, timeline_report, "bftsim_rollcall_last_trace")) return e;
+    bftsim_audit_report own;
+    return audit_kept_trace(h, inst_begin, inst_count, key_cap, audit_out, audit_report ? audit_report : &own, nullptr, nullptr,
+                            nullptr, &rc);
+}
+int bftsim_rollcall_last_ms(bftsim_t* h, float* audit_ms, float* timeline_ms, float* views_ms, float* walk_ms, float* gather_ms,
+                            float* copy_ms) {
+    if (!h) return BFTSIM_EINVAL;
+    float* const dst[6] = {audit_ms, timeline_ms, views_ms, walk_ms, gather_ms, copy_ms};
+    for (int k = 0; k < 6; ++k)
+        if (dst[k]) *dst[k] = h->rollcall_ms[k];
     return BFTSIM_OK;
 }
 

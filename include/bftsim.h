@@ -521,6 +521,80 @@ int bftsim_timeline_last_trace(bftsim_t *h, uint64_t inst_begin, uint64_t inst_c
  * them */
 int bftsim_timeline_last_ms(bftsim_t *h, float *audit_ms, float *walk_ms, float *rows_ms, float *copy_ms);
 
+/* the roll call (SPEC.md §11i): which validator failed to do its job. The observer's passes and the chronicler's walk,
+ * then per instance over the frames the observer accepts (status OK or SEAL_FOREIGN, code 1..4) at a height in
+ * 1..max_heights: per validator what it signed, and per view the wire proves started — (x, 0) at x = 1 or above a
+ * commit certificate of x - 1, (x, r > 0) at a quorate RoundChange key of the chronicler — the proposer
+ * (seed(parent) + r mod n) mod n under the handle's seed_byte_order, with the genesis hash or the certificate digest of
+ * x - 1 as the parent, and whether a counting PrePrepare of that proposer at (x, r) is in the instance. Rounds are the
+ * full u64; frame indices are within the instance. */
+#define BFTSIM_ROLLCALL_PROPOSED 1u       /* outcome: the proposer's PrePrepare at the view is in the instance */
+#define BFTSIM_ROLLCALL_MISSED 2u         /* outcome: it is not */
+#define BFTSIM_ROLLCALL_UNATTRIBUTED 3u   /* outcome: height - 1 has no certificate, so the proposer is unknown */
+#define BFTSIM_ROLLCALL_WON 0x100u        /* added to PROPOSED: the height's certificate was completed at this round, and
+                                             one of those PrePrepares carries its digest */
+#define BFTSIM_ROLLCALL_PARTIAL 1u        /* instance flag: the chronicler's key table overflowed (tl_cap): RoundChange
+                                             quorums, and their views, may be missing; what was found stands */
+struct bftsim_rollcall_record {     /* one due view */
+    uint64_t round;
+    uint32_t inst, height;
+    uint32_t proposer;              /* 0xffffffff: unattributed */
+    uint32_t outcome;               /* BFTSIM_ROLLCALL_PROPOSED (| _WON), _MISSED or _UNATTRIBUTED */
+    uint32_t start_frame;           /* the frame that proves the start: the certificate frame of height - 1 (round 0),
+                                       the RoundChange key's completing frame (round > 0); 0xffffffff for (1, 0) */
+    uint32_t pp_frame;              /* the first counting PrePrepare of the proposer at the view, 0xffffffff: none */
+};
+typedef struct bftsim_rollcall_record bftsim_rollcall_record;
+struct bftsim_rollcall_report {
+    uint64_t frames;                /* counting frames */
+    uint64_t out_of_range;          /* accepted frames at height 0 or above max_heights */
+    uint64_t views;                 /* due views, whatever rec_cap */
+    uint64_t by_outcome[3];         /* PROPOSED (with or without WON), MISSED, UNATTRIBUTED */
+    uint64_t won;                   /* views with BFTSIM_ROLLCALL_WON */
+    uint64_t silent;                /* (instance, validator) pairs without a counting frame */
+    uint64_t silent_instances;      /* instances with at least one */
+    uint64_t partial_instances;     /* instances with BFTSIM_ROLLCALL_PARTIAL */
+};
+typedef struct bftsim_rollcall_report bftsim_rollcall_report;
+struct bftsim_rollcall_out {        /* host, caller-owned, any pointer may be NULL; rows = inst_count * n, row inst * n + v */
+    uint32_t *frames;               /* [rows * 4] the counting frames v signed, by code 1..4 */
+    uint32_t *last_height;          /* [rows] the greatest height among them, 0: none */
+    uint32_t *last_frame;           /* [rows] v's last counting frame, 0xffffffff: none */
+    uint32_t *due;                  /* [rows] the instance's attributed views whose proposer is v */
+    uint32_t *proposed;             /* [rows] those with outcome PROPOSED */
+    uint32_t *missed;               /* [rows] those with outcome MISSED */
+    uint32_t *won;                  /* [rows] those with WON */
+    uint32_t *inst_views;           /* [inst_count] due views of the instance */
+    uint64_t *inst_silent;          /* [inst_count * 4] bitmap of the validators without a counting frame */
+    uint32_t *inst_flags;           /* [inst_count] BFTSIM_ROLLCALL_PARTIAL */
+    bftsim_rollcall_record *records;/* [rec_cap] the first min(report.views, rec_cap) views, instance-major, within an
+                                       instance by (height, round) ascending */
+    uint64_t rec_cap;
+};
+typedef struct bftsim_rollcall_out bftsim_rollcall_out;
+/* stream .. key_cap, audit_out and audit_report (both nullable): as bftsim_audit_trace, whose refusals are this call's
+ * and whose outputs those two receive unchanged; tl_cap, timeline_out and timeline_report (both nullable): as
+ * bftsim_timeline_trace, likewise. An instance has at most max_heights + tl_cap views, and its table has that many
+ * slots. BFTSIM_EINVAL too for a null out or report, for rec_cap above 0 without records, and for a handle of more than
+ * 256 validators; BFTSIM_ENOMEM, before anything is launched, for tables the device cannot hold. A refused call writes
+ * nothing; hostile frame contents are never an error (a RoundChange quorum at round 2^60 is one view); the handle's run
+ * state is untouched; no secrets are needed. */
+int bftsim_rollcall_trace(bftsim_t *h, const uint8_t *stream, uint64_t stream_bytes, const uint64_t *frame_off, uint64_t frames,
+                          const uint64_t *inst_frame0, uint64_t inst_count, uint32_t max_heights, uint32_t key_cap,
+                          uint32_t tl_cap, const bftsim_rollcall_out *out, bftsim_rollcall_report *report,
+                          const bftsim_audit_out *audit_out, bftsim_audit_report *audit_report,
+                          const bftsim_timeline_out *timeline_out, bftsim_timeline_report *timeline_report);
+/* the same over the kept trace of the last launch, as bftsim_audit_last_trace: the stream never leaves the device */
+int bftsim_rollcall_last_trace(bftsim_t *h, uint64_t inst_begin, uint64_t inst_count, uint32_t key_cap, uint32_t tl_cap,
+                               const bftsim_rollcall_out *out, bftsim_rollcall_report *report,
+                               const bftsim_audit_out *audit_out, bftsim_audit_report *audit_report,
+                               const bftsim_timeline_out *timeline_out, bftsim_timeline_report *timeline_report);
+/* diagnostics: device times (ms, HIP events) of the last roll call: the observer's passes, the chronicler's walk + rows,
+ * then the views kernel, the walk kernel (with its fold), scan + gather, and the copies, as scripts/rollcall_bench.py
+ * records them */
+int bftsim_rollcall_last_ms(bftsim_t *h, float *audit_ms, float *timeline_ms, float *views_ms, float *walk_ms,
+                            float *gather_ms, float *copy_ms);
+
 /* the importer (SPEC.md §11d): what a syncing node runs on every Header it is handed, Engine::verify_header with
  * seal = true and verify_seal (src/consensus/backend.rs:319-367), batched: every header of every instance's ledger,
  * verified from untrusted bytes on the device.
