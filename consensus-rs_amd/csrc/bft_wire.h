@@ -263,6 +263,11 @@ BFT_FN bool decode_frame(const uint8_t* f, uint32_t len, Decoded& d) {
     Mem m{f + 4, len - 4u, 0};
     return decode_body(m, d);
 }
+// what bftwire_decode takes (the GPU kernel and the host build alike): a frame of at most MAX_FRAME bytes, the
+// reference's MAX_MSG_SIZE (codec.rs:12). The observer calls decode_frame and bounds the span itself (bft_audit.h MAX_SPAN).
+BFT_FN bool decode_frame_bounded(const uint8_t* f, uint64_t len, Decoded& d) {
+    return len <= MAX_FRAME && decode_frame(f, (uint32_t)len, d);
+}
 
 }  // namespace wire
 }  // namespace bft

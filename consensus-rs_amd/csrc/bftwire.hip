@@ -227,7 +227,7 @@ __global__ __launch_bounds__(64) void wire_decode_kernel(const uint8_t* stream, 
     if (i >= n) return;
     const uint64_t o = off[i], len = off[i + 1] - o;
     Decoded d;
-    const bool good = len <= MAX_FRAME && decode_frame(stream + o, (uint32_t)len, d);
+    const bool good = decode_frame_bounded(stream + o, len, d);
     out.code[i] = good ? (uint8_t)d.code : 0;
     out.round[i] = good ? d.round : 0;
     out.height[i] = good ? d.height : 0;

@@ -107,7 +107,9 @@ int bftwire_decode_preprepare(bftwire_t *h, const uint8_t *stream, const uint64_
 int bftwire_encode_blocks(bftwire_t *h, const bftwire_block *blocks, const uint64_t *block_off, uint64_t n_frames,
                           const uint64_t *ttl, const uint64_t *raw_time, uint8_t *stream, uint64_t cap,
                           uint64_t *frame_off, uint8_t *ok, void *stream_);
-/* frame k's blocks into out[k * max_per_frame ..], their number into count[k] (ok = 0 beyond max) */
+/* frame k's blocks into out[k * max_per_frame ..], their number into count[k] (ok = 0 beyond max). Nothing outside
+ * frame k's own max_per_frame slots is written, and of an accepted frame only its first count[k] slots. A rejected
+ * frame has ok = 0 and count = 0; what its slots hold is unspecified (the blocks decoded before the fault was met). */
 int bftwire_decode_blocks(bftwire_t *h, const uint8_t *stream, const uint64_t *frame_off, uint64_t n_frames,
                           uint32_t max_per_frame, bftwire_block *out, uint32_t *count, uint8_t *ok, void *stream_);
 /* Sync frames: RawMessage{Sync, payload = Height} (core.rs:80-85) */

@@ -50,8 +50,9 @@ def encode(m: dict) -> tuple[bytes, bytes, bytes]:
     return frame(g, m.get("ttl", 10), m.get("raw_time", 0), m.get("peer_id")), g, sp
 
 
-def decode(fr: bytes) -> dict | None:
-    """frame -> fields, or None when it is not a well-formed Subject-carrying Consensus frame."""
+def loose_decode(fr: bytes) -> dict | None:
+    """frame -> fields by msgpack.unpackb, which checks few types: looser than the grammar of SPEC.md §9. Kept to
+    cross-check wire_strict on well-formed frames; `decode` below is the reference."""
     try:
         if len(fr) < 4 or struct.unpack(">I", fr[:4])[0] != len(fr) - 4:
             return None
@@ -170,7 +171,7 @@ def block_from_obj(o):
     return b
 
 
-def decode_preprepare(fr: bytes) -> dict | None:
+def loose_decode_preprepare(fr: bytes) -> dict | None:
     try:
         env = _envelope(fr, P2P_CONSENSUS)
         if env is None:
@@ -189,7 +190,7 @@ def decode_preprepare(fr: bytes) -> dict | None:
         return None
 
 
-def decode_blocks(fr: bytes):
+def loose_decode_blocks(fr: bytes):
     try:
         env = _envelope(fr, P2P_BLOCK)
         return None if env is None else [block_from_obj(o) for o in msgpack.unpackb(env[0])]
@@ -197,7 +198,7 @@ def decode_blocks(fr: bytes):
         return None
 
 
-def decode_sync(fr: bytes):
+def loose_decode_sync(fr: bytes):
     try:
         env = _envelope(fr, P2P_SYNC)
         if env is None:
@@ -206,3 +207,24 @@ def decode_sync(fr: bytes):
         return h if isinstance(h, int) and h >= 0 else None
     except Exception:
         return None
+
+
+# ---- the decoders: the strict reference of SPEC.md §9's decoder grammar (oracle/wire_strict.py) --------------------
+import wire_strict as _strict  # noqa: E402
+
+
+def decode(fr: bytes) -> dict | None:
+    """frame -> fields, or None when it is not a well-formed Subject-carrying Consensus frame."""
+    return _strict.decode(bytes(fr))
+
+
+def decode_preprepare(fr: bytes) -> dict | None:
+    return _strict.decode_preprepare(bytes(fr))
+
+
+def decode_blocks(fr: bytes, max_per_frame: int | None = None):
+    return _strict.decode_blocks(bytes(fr), max_per_frame)
+
+
+def decode_sync(fr: bytes):
+    return _strict.decode_sync(bytes(fr))

@@ -79,6 +79,24 @@ def oracle_recover(digests: np.ndarray, sigs: np.ndarray):
     return addr, ok
 
 
+def records(frames, cfg, max_heights: int) -> dict:
+    """the decode pass alone over a list of frames: its per-frame records (st, code, hx, round, digest, sdig, sig,
+    seal_k, pp_want) and the dense seal list (seal_dig, seal, n_seals)"""
+    L = lib()
+    stream = np.frombuffer(b"".join(frames) + b"\0", np.uint8)
+    off = np.zeros(len(frames) + 1, np.uint64)
+    off[1:] = np.cumsum([len(f) for f in frames])
+    F = max(len(frames), 1)
+    rec = dict(st=np.zeros(F, np.uint8), code=np.zeros(F, np.uint8), hx=np.zeros(F, np.uint32),
+               round=np.zeros(F, np.uint64), digest=np.zeros((F, 32), np.uint8), sdig=np.zeros((F, 32), np.uint8),
+               sig=np.zeros((F, 65), np.uint8), seal_k=np.zeros(F, np.uint32), pp_want=np.zeros(F, np.uint32),
+               seal_dig=np.zeros((F, 32), np.uint8), seal=np.zeros((F, 65), np.uint8))
+    r = Recs(*[a.ctypes.data for a in rec.values()])
+    rec["n_seals"] = L.audit_host_decode(stream.ctypes.data, off.ctypes.data, len(frames), cfg.address_bytes(), cfg.n,
+                                         cfg.seed_byte_order, max_heights, ctypes.byref(r))
+    return rec
+
+
 def observe(stream, frame_off, inst_frame0, cfg, max_heights: int, key_cap: int = 0) -> dict:
     """The host build over a frame stream: the arrays of bftsim_audit_out (shaped as bftsim.trace.Audit shapes them),
     `report` (a dict of bftsim_audit_report) and `recs` (the decode pass's records)."""
@@ -122,7 +140,11 @@ def observe(stream, frame_off, inst_frame0, cfg, max_heights: int, key_cap: int 
                 report=report, recs=rec)
 
 
-def san_input(addresses: bytes, n: int, frames) -> bytes:
-    """stdin of the stand-alone program (tests/emu/audit_host.cpp)"""
-    return struct.pack("<I", n) + addresses + struct.pack("<I", len(frames)) + \
+def san_input(addresses: bytes, n: int, frames, catalogue=None) -> bytes:
+    """stdin of the stand-alone program (tests/emu/audit_host.cpp); catalogue: [(frame, decodable)] or None"""
+    out = struct.pack("<I", n) + addresses + struct.pack("<I", len(frames)) + \
         b"".join(struct.pack("<I", len(f)) + f for f in frames)
+    if catalogue is not None:
+        out += struct.pack("<I", len(catalogue)) + b"".join(bytes([int(bool(ok))]) + struct.pack("<I", len(f)) + f
+                                                            for f, ok in catalogue)
+    return out

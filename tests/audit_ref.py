@@ -1,6 +1,6 @@
 """CPU reference of the observer (SPEC.md §11c), test infrastructure only: frame bytes -> statuses, signers, commit
-certificates and the safety verdict, with msgpack (through oracle/wire_ref.py), the C oracle's secp256k1 recovery and
-Keccak-256. Independent of the code under test: no byte of it comes from csrc/."""
+certificates and the safety verdict, with the strict wire reference (oracle/wire_strict.py; the msgpack encoders of
+oracle/wire_ref.py), the C oracle's secp256k1 recovery and Keccak-256. Independent of the code under test: no byte of it comes from csrc/."""
 from __future__ import annotations
 
 import os
@@ -12,6 +12,7 @@ import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle"))
 import oracle_lib as O  # noqa: E402
 import wire_ref as R  # noqa: E402
+import wire_strict as WS  # noqa: E402
 
 ST_OK, ST_UNDECODABLE, ST_UNRECOVERABLE, ST_NOT_VALIDATOR, ST_SEAL_BAD, ST_SEAL_FOREIGN = range(6)
 KEY_OVERFLOW, CONFLICT = 1, 2
@@ -25,7 +26,14 @@ def _uint(x):
 
 
 def parse(fr: bytes):
-    """frame -> dict(code, round, height, digest, sign_payload, sig, seal, block) or None (UNDECODABLE)"""
+    """frame -> dict(code, round, height, digest, sign_payload, sig, seal, block) or None (UNDECODABLE): the strict
+    reference of SPEC.md §9's decoder grammar with the observer's rules of §11c row 1 (oracle/wire_strict.py)"""
+    return WS.observe_parse(bytes(fr))
+
+
+def parse_loose(fr: bytes):
+    """the same by msgpack.unpackb, which checks fewer types than the grammar: kept to cross-check `parse` on
+    well-formed frames"""
     try:
         env = R._envelope(fr, R.P2P_CONSENSUS)
         if env is None:

@@ -2,7 +2,8 @@
 // and tally step the observer's kernels run), checked against tests/audit_ref.py on the CPU. As a shared library
 // (tests/audit_lib.py) it runs the observer in two halves with the recoveries, taken from the C oracle, in between;
 // with -DAUDIT_HOST_MAIN it is a stand-alone program for the sanitizers: it reads frames from stdin and parses every
-// truncation and every single-byte flip of each, from heap buffers of exactly the frame's length.
+// truncation and every single-byte flip of each, from heap buffers of exactly the frame's length; then, if more follows,
+// the catalogue of tests/wire_mutations.py with the strict reference's verdicts, each frame parsed the same way.
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -105,7 +106,8 @@ void audit_host_finish(const Recs* rp, uint64_t frames, const uint8_t* addresses
 }
 
 #ifdef AUDIT_HOST_MAIN
-// stdin: u32 n, u8 addresses[n][20], u32 count, then per frame {u32 len, u8 frame[len]} (little-endian)
+// stdin: u32 n, u8 addresses[n][20], u32 count, then per frame {u32 len, u8 frame[len]} (little-endian); optionally
+// u32 cases, then per case {u8 decodable, u32 len, u8 frame[len]}
 static bool rd(void* p, size_t n) { return fread(p, 1, n, stdin) == n; }
 struct OneRec {
     uint8_t st, code, digest[32], sdig[32], sig[65], seal_dig[32], seal[65];
@@ -146,6 +148,18 @@ int main() {
             }
     }
     printf("ok %u frames %llu cases\n", count, (unsigned long long)cases);
+    uint32_t ncat = 0;
+    if (!rd(&ncat, 4)) return 0;                                   // no catalogue
+    for (uint32_t k = 0; k < ncat; ++k) {
+        uint8_t want = 0;
+        uint32_t len = 0;
+        if (!rd(&want, 1) || !rd(&len, 4) || len > (1u << 20)) return 2;
+        std::vector<uint8_t> fr(len);
+        if (!rd(fr.data(), len)) return 2;
+        const uint32_t st = parse_exact(fr.data(), len, addr.data(), n);
+        if (st != (want ? (uint32_t)ST_OK : (uint32_t)ST_UNDECODABLE)) { printf("case %u: status %u, decodable %u\n", k, st, want); return 1; }
+    }
+    printf("catalogue ok %u cases\n", ncat);
     return 0;
 }
 #endif

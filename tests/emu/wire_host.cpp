@@ -1,5 +1,7 @@
 // wire_host.cpp — TEST-ONLY host build of consensus-rs_amd/csrc/bft_wire.h (the serial encoder and
-// streaming decoder the GPU kernels share), checked against oracle/wire_ref.py on the CPU.
+// streaming decoder the GPU kernels share), checked against oracle/wire_ref.py on the CPU. With -DWIRE_HOST_MAIN it is
+// a stand-alone program for the sanitizers: it reads the catalogue of tests/wire_mutations.py with the verdicts of the
+// strict reference from stdin and runs the four decoders on every frame, from a heap buffer of exactly its length.
 #include <stdint.h>
 #include <string.h>
 
@@ -19,7 +21,7 @@ uint32_t wire_host_encode(uint32_t code, uint64_t round, uint64_t height, const 
     *splen = encode_gossip(sp, MAX_G, code, ctime, s, ls, nullptr, seal);
     return encode_frame(frame, MAX_FRAME, ttl, rtime, peer, peer_len, g, *glen);
 }
-int wire_host_decode(const uint8_t* f, uint32_t len, Decoded* d) { return decode_frame(f, len, *d) ? 1 : 0; }
+int wire_host_decode(const uint8_t* f, uint32_t len, Decoded* d) { return decode_frame_bounded(f, len, *d) ? 1 : 0; }
 uint32_t wire_host_decoded_size() { return (uint32_t)sizeof(Decoded); }
 }
 
@@ -87,3 +89,37 @@ uint32_t wire_host_sync_encode(uint64_t height, uint64_t ttl, uint64_t rt, uint8
 }
 int wire_host_sync_decode(const uint8_t* f, uint32_t len, uint64_t* height) { return decode_sync_frame(f, len, *height) ? 1 : 0; }
 }
+
+#ifdef WIRE_HOST_MAIN
+#include <stdio.h>
+#include <stdlib.h>
+
+#include <vector>
+// stdin: u32 max_per_frame, u32 count, then per case {u8 want[4] (decode, decode_preprepare, decode_blocks,
+// decode_sync: 1 accepted), u32 len, u8 frame[len]} (little-endian)
+static bool rd(void* p, size_t n) { return fread(p, 1, n, stdin) == n; }
+int main() {
+    uint32_t maxpf = 0, count = 0;
+    if (!rd(&maxpf, 4) || maxpf < 1 || maxpf > 64 || !rd(&count, 4)) return 2;
+    std::vector<bftwire_block> blocks(maxpf);
+    bftwire_preprepare* pp = (bftwire_preprepare*)malloc(sizeof(bftwire_preprepare));
+    for (uint32_t k = 0; k < count; ++k) {
+        uint8_t want[4];
+        uint32_t len = 0;
+        if (!rd(want, 4) || !rd(&len, 4) || len > (1u << 20)) return 2;
+        uint8_t* f = (uint8_t*)malloc(len ? len : 1);          // exactly the frame: a read past it is caught
+        if (!rd(f, len)) return 2;
+        Decoded d;
+        uint32_t cnt = 0;
+        uint64_t height = 0;
+        const int got[4] = {wire_host_decode(f, len, &d), wire_host_pp_decode(f, len, pp),
+                            wire_host_blocks_decode(f, len, blocks.data(), maxpf, &cnt), wire_host_sync_decode(f, len, &height)};
+        free(f);
+        for (int e = 0; e < 4; ++e)
+            if (got[e] != (int)want[e]) { printf("case %u entry %d: got %d, want %d\n", k, e, got[e], (int)want[e]); return 1; }
+    }
+    free(pp);
+    printf("ok %u cases\n", count);
+    return 0;
+}
+#endif

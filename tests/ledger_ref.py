@@ -14,122 +14,22 @@ import crypto_ref as C          # first: it puts oracle/ on the path
 import oracle_lib as O
 import sig_lib
 import trace_ref as TR
+import wire_strict as WS
 
 (OK, ABSENT, UNDECODABLE, BAD_HEIGHT, NO_PARENT, BAD_PARENT, BAD_TIME, LACK_VOTES, BAD_VOTE, BAD_PROPOSER) = range(10)
 MAX_EXTRA, MAX_VOTES = 32, 256
 ARRAYS = ("status", "block_hash", "voters", "n_votes", "verified_height")
 
 
-class _Bad(Exception):
-    pass
-
-
-class _Reader:
-    """MessagePack as the reference's serializer writes it and serde reads it back (SPEC.md §9): unsigned integers in
-    any of their widths, arrays in any of theirs, strings for addresses; nothing else"""
-
-    def __init__(self, b: bytes):
-        self.b, self.i = b, 0
-
-    def get(self) -> int:
-        if self.i >= len(self.b):
-            raise _Bad
-        self.i += 1
-        return self.b[self.i - 1]
-
-    def be(self, k: int) -> int:
-        v = 0
-        for _ in range(k):
-            v = (v << 8) | self.get()
-        return v
-
-    def uint_tag(self, t: int) -> int:
-        if t < 0x80:
-            return t
-        if t in (0xcc, 0xcd, 0xce, 0xcf):
-            return self.be(1 << (t - 0xcc))
-        raise _Bad
-
-    def uint(self) -> int:
-        return self.uint_tag(self.get())
-
-    def arr_tag(self, t: int) -> int:
-        if t & 0xf0 == 0x90:
-            return t & 15
-        if t == 0xdc:
-            return self.be(2)
-        if t == 0xdd:
-            return self.be(4)
-        raise _Bad
-
-    def arr(self) -> int:
-        return self.arr_tag(self.get())
-
-    def byte_list(self, n: int) -> bytes:
-        out = bytearray()
-        for _ in range(n):
-            v = self.uint()
-            if v > 255:
-                raise _Bad
-            out.append(v)
-        return bytes(out)
-
-    def fixed(self, n: int) -> bytes:
-        if self.arr() != n:
-            raise _Bad
-        return self.byte_list(n)
-
-    def address(self) -> bytes:
-        t = self.get()
-        if t == 0xd9:
-            n = self.be(1)
-        elif t & 0xe0 == 0xa0:
-            n = t & 31
-        elif t == 0xda:
-            n = self.be(2)
-        else:
-            raise _Bad
-        if n != 42:
-            raise _Bad
-        s = bytes(self.get() for _ in range(42))
-        if s[:1] != b"0" or s[1:2] not in (b"x", b"X"):
-            raise _Bad
-        try:
-            txt = s[2:].decode("ascii")
-            if any(c not in "0123456789abcdefABCDEF" for c in txt):
-                raise _Bad
-            return bytes.fromhex(txt)
-        except (UnicodeDecodeError, ValueError):
-            raise _Bad
+_Bad, _Reader = WS.Bad, WS.Reader          # the strict MessagePack reader of SPEC.md §9's decoder grammar
 
 
 def decode(b: bytes):
     """header bytes -> dict of its fields (votes: None or a list of 65-byte strings), or None when undecodable"""
-    r = _Reader(b)
+    r = _Reader(bytes(b))
     try:
-        hf = r.arr()
-        if not 11 <= hf <= 13:
-            raise _Bad
-        d = dict(prev_hash=r.fixed(32), proposer=r.address(), root=r.fixed(32), tx_hash=r.fixed(32), receipt_hash=r.fixed(32))
-        for k in ("bloom", "difficulty", "height", "gas_limit", "gas_used", "time"):
-            d[k] = r.uint()
-        d["extra"], d["votes"] = None, None
-        if hf >= 12:
-            t = r.get()
-            if t != 0xc0:
-                n = r.arr_tag(t)
-                if n > MAX_EXTRA:
-                    raise _Bad
-                d["extra"] = r.byte_list(n)
-        if hf >= 13:
-            t = r.get()
-            if t != 0xc0:
-                n = r.arr_tag(t)
-                if n > MAX_VOTES:
-                    raise _Bad
-                d["votes"] = [r.fixed(65) for _ in range(n)]
-        if r.i != len(b):
-            raise _Bad
+        d = WS.read_header(r, MAX_VOTES, MAX_EXTRA)
+        r.end()
         return d
     except _Bad:
         return None

@@ -13,6 +13,8 @@ SRCS = [os.path.join(EMU_DIR, "wire_host.cpp")] + [
     os.path.join(ROOT, "consensus-rs_amd", "csrc", f) for f in ("bft_wire.h", "bft_common.h", "bft_wire_block.h",
                                                                "bft_crypto.h")] + [
     os.path.join(ROOT, "include", "bftwire.h")]
+SAN_EXE = os.path.join(EMU_DIR, "_san", "wire_san")
+SAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-g", "-O1"]
 _lib = None
 
 
@@ -30,6 +32,24 @@ def build():
     tmp = f"{LIB}.{os.getpid()}.tmp"      # private name + rename: safe under concurrent test workers
     subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-Wno-unknown-pragmas", "-o", tmp, SRCS[0]])
     os.replace(tmp, LIB)
+
+
+def build_san():
+    """the stand-alone program (its own main) under AddressSanitizer + UBSan; never loaded into python"""
+    if os.path.exists(SAN_EXE) and all(os.path.getmtime(SAN_EXE) >= os.path.getmtime(s) for s in SRCS):
+        return SAN_EXE
+    os.makedirs(os.path.dirname(SAN_EXE), exist_ok=True)
+    tmp = f"{SAN_EXE}.{os.getpid()}.tmp"
+    subprocess.check_call(["g++", "-std=c++17", "-Wno-unknown-pragmas", "-DWIRE_HOST_MAIN", "-o", tmp, SRCS[0]] + SAN)
+    os.replace(tmp, SAN_EXE)
+    return SAN_EXE
+
+
+def san_input(max_per_frame: int, cases) -> bytes:
+    """stdin of the stand-alone program (tests/emu/wire_host.cpp); cases: [(frame, [4 verdicts])]"""
+    import struct
+    return struct.pack("<II", max_per_frame, len(cases)) + b"".join(
+        bytes(int(bool(w)) for w in want) + struct.pack("<I", len(f)) + f for f, want in cases)
 
 
 def lib():
