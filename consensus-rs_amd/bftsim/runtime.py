@@ -371,10 +371,7 @@ class Simulator:
 
     def trace_twins_ms(self):
         """(mark + scan + merge, digests, signing) of the last verify's twin passes, device ms."""
-        a, b, c = ctypes.c_float(), ctypes.c_float(), ctypes.c_float()
-        _check(self.h, lib().bftsim_trace_twins_last_ms(self.h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)),
-               "bftsim_trace_twins_last_ms")
-        return a.value, b.value, c.value
+        return self._last_ms("bftsim_trace_twins_last_ms", 3)
 
     def trace_sizes(self):
         """(frames [n] u32, stream bytes [n] u64) per instance of the last launch's trace (after crypto_verify)."""
@@ -401,25 +398,42 @@ class Simulator:
                                                  frames, meta.ctypes.data, f0.ctypes.data), "bftsim_export_trace")
         return Trace(stream, off, meta, f0, begin)
 
+    def _host_trace(self, trace, max_heights):
+        """what the *_trace methods pass on of a bftsim.trace.Trace, or anything with its stream / frame_off /
+        inst_frame0 -> (stream, frame_off, inst_frame0, frames, instances, max_heights, the heights buffers are sized
+        by: 0 where the library refuses max_heights)"""
+        H = self.cfg.heights if max_heights is None else max_heights
+        stream = np.ascontiguousarray(trace.stream, np.uint8)
+        off = np.ascontiguousarray(trace.frame_off, np.uint64)
+        f0 = np.ascontiguousarray(trace.inst_frame0, np.uint64)
+        return stream, off, f0, len(off) - 1, len(f0) - 1, H, H if 0 < H <= 65535 else 0
+
+    def _kept_range(self, what, begin, count):
+        """instances [begin, begin + count) of the kept trace (count None: to the launch's end) -> (count, frames)"""
+        if count is None:
+            count = self.n_launched - begin
+        fr, _ = self.trace_sizes()
+        if begin < 0 or count < 0 or begin + count > len(fr):
+            raise BftsimError(f"{what}: instances [{begin}, {begin + count}) outside the last launch of {len(fr)}")
+        return count, int(fr[begin:begin + count].sum())
+
+    def _last_ms(self, getter, k):
+        """the k phase times, device ms, that a *_last_ms entry point stores"""
+        v = [ctypes.c_float() for _ in range(k)]
+        _check(self.h, getattr(lib(), getter)(self.h, *[ctypes.byref(x) for x in v]), getter)
+        return tuple(x.value for x in v)
+
     def trace_ms(self):
         """(size pass + scan, emit kernel, device-to-host copies) of the last trace calls, device ms."""
-        a, b, c = ctypes.c_float(), ctypes.c_float(), ctypes.c_float()
-        _check(self.h, lib().bftsim_trace_last_ms(self.h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)),
-               "bftsim_trace_last_ms")
-        return a.value, b.value, c.value
+        return self._last_ms("bftsim_trace_last_ms", 3)
 
     def audit_trace(self, trace, max_heights: int = None, key_cap: int = 0):
         """The observer (include/bftsim.h bftsim_audit_trace, SPEC.md §11c) over a bftsim.trace.Trace, or anything
         with its stream / frame_off / inst_frame0: per-frame statuses and signers, per-height commit certificates and
         the safety verdict, all computed on the device from the bytes. -> bftsim.trace.Audit"""
         from .trace import Audit
-        H = self.cfg.heights if max_heights is None else max_heights
-        stream = np.ascontiguousarray(trace.stream, np.uint8)
-        off = np.ascontiguousarray(trace.frame_off, np.uint64)
-        f0 = np.ascontiguousarray(trace.inst_frame0, np.uint64)
-        frames, n = len(off) - 1, len(f0) - 1
-        ok = 0 < H <= 65535                        # the library refuses it; no buffers are sized by it here
-        o, arrs = _abi.alloc_audit(frames, n, H if ok else 0)
+        stream, off, f0, frames, n, H, Hb = self._host_trace(trace, max_heights)
+        o, arrs = _abi.alloc_audit(frames, n, Hb)
         rep = _abi.CAuditReport()
         _check(self.h, lib().bftsim_audit_trace(self.h, stream.ctypes.data, len(stream), off.ctypes.data, frames,
                                                 f0.ctypes.data, n, H, key_cap, ctypes.byref(o), ctypes.byref(rep)),
@@ -430,12 +444,8 @@ class Simulator:
         """The same over the kept trace of the last launch (after crypto_verify with set_trace_keep), instances
         [begin, begin + count): emitted and audited on the device (bftsim_audit_last_trace)."""
         from .trace import Audit
-        if count is None:
-            count = self.n_launched - begin
-        fr, _ = self.trace_sizes()
-        if begin < 0 or count < 0 or begin + count > len(fr):
-            raise BftsimError(f"audit_last_trace: instances [{begin}, {begin + count}) outside the last launch of {len(fr)}")
-        o, arrs = _abi.alloc_audit(int(fr[begin:begin + count].sum()), count, self.cfg.heights)
+        count, frames = self._kept_range("audit_last_trace", begin, count)
+        o, arrs = _abi.alloc_audit(frames, count, self.cfg.heights)
         rep = _abi.CAuditReport()
         _check(self.h, lib().bftsim_audit_last_trace(self.h, begin, count, key_cap, ctypes.byref(o), ctypes.byref(rep)),
                "bftsim_audit_last_trace")
@@ -443,9 +453,7 @@ class Simulator:
 
     def audit_ms(self):
         """(decode, recoveries, classify + tally, copies) of the last audit, device ms (bftsim_audit_last_ms)."""
-        v = [ctypes.c_float() for _ in range(4)]
-        _check(self.h, lib().bftsim_audit_last_ms(self.h, *[ctypes.byref(x) for x in v]), "bftsim_audit_last_ms")
-        return tuple(x.value for x in v)
+        return self._last_ms("bftsim_audit_last_ms", 4)
 
     def archive_trace(self, trace, max_heights: int = None, key_cap: int = 0):
         """The archiver (include/bftsim.h bftsim_archive_trace, SPEC.md §11e) over a bftsim.trace.Trace, or anything with
@@ -454,15 +462,10 @@ class Simulator:
         ledger is the (hdr, hdr_len, slot_bytes, heights) that verify_ledger takes."""
         from .ledger import Archive
         from .trace import Audit
-        H = self.cfg.heights if max_heights is None else max_heights
-        stream = np.ascontiguousarray(trace.stream, np.uint8)
-        off = np.ascontiguousarray(trace.frame_off, np.uint64)
-        f0 = np.ascontiguousarray(trace.inst_frame0, np.uint64)
-        frames, n = len(off) - 1, len(f0) - 1
-        ok = 0 < H <= 65535                        # the library refuses it; no buffers are sized by it here
+        stream, off, f0, frames, n, H, Hb = self._host_trace(trace, max_heights)
         slot = lib().bftsim_ledger_slot_bytes(self.cfg.n)
-        hdr, lens, o, arrs = _abi.alloc_archive(n, H if ok else 0, slot)
-        ao, aarrs = _abi.alloc_audit(frames, n, H if ok else 0)
+        hdr, lens, o, arrs = _abi.alloc_archive(n, Hb, slot)
+        ao, aarrs = _abi.alloc_audit(frames, n, Hb)
         rep, arep = _abi.CArchiveReport(), _abi.CAuditReport()
         _check(self.h, lib().bftsim_archive_trace(self.h, stream.ctypes.data, len(stream), off.ctypes.data, frames,
                                                   f0.ctypes.data, n, H, key_cap, hdr.ctypes.data, slot, lens.ctypes.data,
@@ -475,15 +478,11 @@ class Simulator:
         [begin, begin + count): emitted, audited and archived on the device (bftsim_archive_last_trace)."""
         from .ledger import Archive
         from .trace import Audit
-        if count is None:
-            count = self.n_launched - begin
-        fr, _ = self.trace_sizes()
-        if begin < 0 or count < 0 or begin + count > len(fr):
-            raise BftsimError(f"archive_last_trace: instances [{begin}, {begin + count}) outside the last launch of {len(fr)}")
+        count, frames = self._kept_range("archive_last_trace", begin, count)
         H = self.cfg.heights
         slot = lib().bftsim_ledger_slot_bytes(self.cfg.n)
         hdr, lens, o, arrs = _abi.alloc_archive(count, H, slot)
-        ao, aarrs = _abi.alloc_audit(int(fr[begin:begin + count].sum()), count, H)
+        ao, aarrs = _abi.alloc_audit(frames, count, H)
         rep, arep = _abi.CArchiveReport(), _abi.CAuditReport()
         _check(self.h, lib().bftsim_archive_last_trace(self.h, begin, count, key_cap, hdr.ctypes.data, slot, lens.ctypes.data,
                                                        ctypes.byref(o), ctypes.byref(ao), ctypes.byref(arep), ctypes.byref(rep)),
@@ -493,9 +492,7 @@ class Simulator:
     def archive_ms(self):
         """(the observer's passes, pick, emit + heights, copies) of the last archive call, device ms
         (bftsim_archive_last_ms)."""
-        v = [ctypes.c_float() for _ in range(4)]
-        _check(self.h, lib().bftsim_archive_last_ms(self.h, *[ctypes.byref(x) for x in v]), "bftsim_archive_last_ms")
-        return tuple(x.value for x in v)
+        return self._last_ms("bftsim_archive_last_ms", 4)
 
     def accuse_trace(self, trace, max_heights: int = None, key_cap: int = 0, view_cap: int = 0, rec_cap: int = None):
         """The accuser (include/bftsim.h bftsim_accuse_trace, SPEC.md §11g) over a bftsim.trace.Trace, or anything with
@@ -503,14 +500,9 @@ class Simulator:
         among the frames the observer accepts, each with the two frames that prove it, found on the device.
         -> bftsim.trace.Accusation (its .audit: the observer's outputs of the same call)"""
         from .trace import Accusation, Audit
-        H = self.cfg.heights if max_heights is None else max_heights
-        stream = np.ascontiguousarray(trace.stream, np.uint8)
-        off = np.ascontiguousarray(trace.frame_off, np.uint64)
-        f0 = np.ascontiguousarray(trace.inst_frame0, np.uint64)
-        frames, n = len(off) - 1, len(f0) - 1
-        ok = 0 < H <= 65535                        # the library refuses it; no buffers are sized by it here
+        stream, off, f0, frames, n, H, Hb = self._host_trace(trace, max_heights)
         o, arrs = _abi.alloc_accuse(frames, n, rec_cap)
-        ao, aarrs = _abi.alloc_audit(frames, n, H if ok else 0)
+        ao, aarrs = _abi.alloc_audit(frames, n, Hb)
         rep, arep = _abi.CAccuseReport(), _abi.CAuditReport()
         _check(self.h, lib().bftsim_accuse_trace(self.h, stream.ctypes.data, len(stream), off.ctypes.data, frames,
                                                  f0.ctypes.data, n, H, key_cap, view_cap, ctypes.byref(o), ctypes.byref(ao),
@@ -523,12 +515,8 @@ class Simulator:
         second frames are there with set_trace_twins), instances [begin, begin + count): emitted, audited and accused on
         the device (bftsim_accuse_last_trace)."""
         from .trace import Accusation, Audit
-        if count is None:
-            count = self.n_launched - begin
-        fr, _ = self.trace_sizes()
-        if begin < 0 or count < 0 or begin + count > len(fr):
-            raise BftsimError(f"accuse_last_trace: instances [{begin}, {begin + count}) outside the last launch of {len(fr)}")
-        frames, H = int(fr[begin:begin + count].sum()), self.cfg.heights
+        count, frames = self._kept_range("accuse_last_trace", begin, count)
+        H = self.cfg.heights
         o, arrs = _abi.alloc_accuse(frames, count, rec_cap)
         ao, aarrs = _abi.alloc_audit(frames, count, H)
         rep, arep = _abi.CAccuseReport(), _abi.CAuditReport()
@@ -540,9 +528,7 @@ class Simulator:
     def accuse_ms(self):
         """(the observer's passes, walk, mark + scan + gather, copies) of the last accuse call, device ms
         (bftsim_accuse_last_ms)."""
-        v = [ctypes.c_float() for _ in range(4)]
-        _check(self.h, lib().bftsim_accuse_last_ms(self.h, *[ctypes.byref(x) for x in v]), "bftsim_accuse_last_ms")
-        return tuple(x.value for x in v)
+        return self._last_ms("bftsim_accuse_last_ms", 4)
 
     def timeline_trace(self, trace, max_heights: int = None, key_cap: int = 0, tl_cap: int = 0):
         """The chronicler (include/bftsim.h bftsim_timeline_trace, SPEC.md §11h) over a bftsim.trace.Trace, or anything
@@ -551,14 +537,9 @@ class Simulator:
         RoundChange frames the observer accepts. -> bftsim.trace.Timeline (its .audit: the observer's outputs of the
         same call)"""
         from .trace import Audit, Timeline
-        H = self.cfg.heights if max_heights is None else max_heights
-        stream = np.ascontiguousarray(trace.stream, np.uint8)
-        off = np.ascontiguousarray(trace.frame_off, np.uint64)
-        f0 = np.ascontiguousarray(trace.inst_frame0, np.uint64)
-        frames, n = len(off) - 1, len(f0) - 1
-        ok = 0 < H <= 65535                        # the library refuses it; no buffers are sized by it here
-        o, arrs = _abi.alloc_timeline(n, H if ok else 0)
-        ao, aarrs = _abi.alloc_audit(frames, n, H if ok else 0)
+        stream, off, f0, frames, n, H, Hb = self._host_trace(trace, max_heights)
+        o, arrs = _abi.alloc_timeline(n, Hb)
+        ao, aarrs = _abi.alloc_audit(frames, n, Hb)
         rep, arep = _abi.CTimelineReport(), _abi.CAuditReport()
         _check(self.h, lib().bftsim_timeline_trace(self.h, stream.ctypes.data, len(stream), off.ctypes.data, frames,
                                                    f0.ctypes.data, n, H, key_cap, tl_cap, ctypes.byref(o), ctypes.byref(ao),
@@ -569,12 +550,8 @@ class Simulator:
         """The same over the kept trace of the last launch (after crypto_verify with set_trace_keep), instances
         [begin, begin + count): emitted, audited and chronicled on the device (bftsim_timeline_last_trace)."""
         from .trace import Audit, Timeline
-        if count is None:
-            count = self.n_launched - begin
-        fr, _ = self.trace_sizes()
-        if begin < 0 or count < 0 or begin + count > len(fr):
-            raise BftsimError(f"timeline_last_trace: instances [{begin}, {begin + count}) outside the last launch of {len(fr)}")
-        frames, H = int(fr[begin:begin + count].sum()), self.cfg.heights
+        count, frames = self._kept_range("timeline_last_trace", begin, count)
+        H = self.cfg.heights
         o, arrs = _abi.alloc_timeline(count, H)
         ao, aarrs = _abi.alloc_audit(frames, count, H)
         rep, arep = _abi.CTimelineReport(), _abi.CAuditReport()
@@ -585,9 +562,7 @@ class Simulator:
 
     def timeline_ms(self):
         """(the observer's passes, walk, rows, copies) of the last timeline call, device ms (bftsim_timeline_last_ms)."""
-        v = [ctypes.c_float() for _ in range(4)]
-        _check(self.h, lib().bftsim_timeline_last_ms(self.h, *[ctypes.byref(x) for x in v]), "bftsim_timeline_last_ms")
-        return tuple(x.value for x in v)
+        return self._last_ms("bftsim_timeline_last_ms", 4)
 
     def _rollcall_result(self, call, what, frames, n, H, rec_cap, tl_cap):
         from .trace import Audit, RollCall, Timeline
@@ -609,34 +584,22 @@ class Simulator:
         its proposer and whether that proposer's PrePrepare is there, found on the device behind the observer and the
         chronicler. rec_cap: every possible view by default (the pages of an np.empty cost nothing until written).
         -> bftsim.trace.RollCall (its .audit and .timeline: their outputs of the same call)"""
-        H = self.cfg.heights if max_heights is None else max_heights
-        stream = np.ascontiguousarray(trace.stream, np.uint8)
-        off = np.ascontiguousarray(trace.frame_off, np.uint64)
-        f0 = np.ascontiguousarray(trace.inst_frame0, np.uint64)
-        frames, n = len(off) - 1, len(f0) - 1
-        ok = 0 < H <= 65535                        # the library refuses it; no buffers are sized by it here
+        stream, off, f0, frames, n, H, Hb = self._host_trace(trace, max_heights)
         call = lambda *tail: lib().bftsim_rollcall_trace(self.h, stream.ctypes.data, len(stream), off.ctypes.data, frames,
                                                          f0.ctypes.data, n, H, key_cap, tl_cap, *tail)
-        return self._rollcall_result(call, "bftsim_rollcall_trace", frames, n, H if ok else 0, rec_cap, tl_cap)
+        return self._rollcall_result(call, "bftsim_rollcall_trace", frames, n, Hb, rec_cap, tl_cap)
 
     def rollcall_last_trace(self, begin: int = 0, count: int = None, key_cap: int = 0, tl_cap: int = 0, rec_cap: int = None):
         """The same over the kept trace of the last launch (after crypto_verify with set_trace_keep), instances
         [begin, begin + count): emitted, audited, chronicled and called on the device (bftsim_rollcall_last_trace)."""
-        if count is None:
-            count = self.n_launched - begin
-        fr, _ = self.trace_sizes()
-        if begin < 0 or count < 0 or begin + count > len(fr):
-            raise BftsimError(f"rollcall_last_trace: instances [{begin}, {begin + count}) outside the last launch of {len(fr)}")
-        frames = int(fr[begin:begin + count].sum())
+        count, frames = self._kept_range("rollcall_last_trace", begin, count)
         call = lambda *tail: lib().bftsim_rollcall_last_trace(self.h, begin, count, key_cap, tl_cap, *tail)
         return self._rollcall_result(call, "bftsim_rollcall_last_trace", frames, count, self.cfg.heights, rec_cap, tl_cap)
 
     def rollcall_ms(self):
         """(the observer's passes, the chronicler's walk + rows, views, walk, scan + gather, copies) of the last roll
         call, device ms (bftsim_rollcall_last_ms)."""
-        v = [ctypes.c_float() for _ in range(6)]
-        _check(self.h, lib().bftsim_rollcall_last_ms(self.h, *[ctypes.byref(x) for x in v]), "bftsim_rollcall_last_ms")
-        return tuple(x.value for x in v)
+        return self._last_ms("bftsim_rollcall_last_ms", 6)
 
     def set_ledger_votes(self, kind: str):
         """What the next crypto_verify keeps as the ledger's votes: "signatures" (the Commit messages' signatures, the
@@ -668,9 +631,7 @@ class Simulator:
 
     def ledger_ms(self):
         """(decode, recoveries, tally + link, copies) of the last verify_ledger, device ms (bftsim_ledger_last_ms)."""
-        v = [ctypes.c_float() for _ in range(4)]
-        _check(self.h, lib().bftsim_ledger_last_ms(self.h, *[ctypes.byref(x) for x in v]), "bftsim_ledger_last_ms")
-        return tuple(x.value for x in v)
+        return self._last_ms("bftsim_ledger_last_ms", 4)
 
     @staticmethod
     def comm_available():

@@ -12,6 +12,30 @@
 #include "bft_wire_block.h"
 
 namespace bft {
+
+// what the trace kernels read of a launch (bftsim.hip): the message log, and what bftsim_crypto_verify kept
+struct TraceArgs {
+    const uint32_t* mlog;
+    uint32_t cap;
+    // dense, per message: kept by bftsim_crypto_verify (bftsim_set_trace_keep)
+    const uint64_t* moff;             // [n_inst + 1]
+    const uint64_t* mref;
+    const uint8_t* raw;
+    const uint32_t* msg_k;
+    const uint8_t* sigs;
+    const uint8_t* seals;
+};
+// twins (bftsim_set_trace_twins, SPEC.md §11f): the merged frame index and, per twin slot, what TraceArgs' dense arrays
+// hold per message. An argument of the twin kernels alone (TwinOpt)
+struct TwinArgs {
+    const uint64_t* fmap;             // [frames] message, | twins::F_TWIN for a twin
+    const uint32_t* tslot;            // [messages + 1] twins before message m: a twin's slot
+    const uint8_t* traw;
+    const uint32_t* tmsg_k;
+    const uint8_t* tsigs;
+    const uint8_t* tseals;
+};
+
 namespace trace {
 
 // what bftsim_crypto_verify derived for one message

@@ -1,4 +1,5 @@
-// bftsim.hip — gfx950 kernels and the C ABI of libbftsim (include/bftsim.h).
+// bftsim.hip — gfx950 kernels and the C ABI of libbftsim (include/bftsim.h), but for the trace analysers and the
+// ledger importer, whose host code is bftsim_observe.hip; what the two files share is bftsim_impl.h.
 //
 // Kernels:
 //   bft_consensus_kernel  one 64-lane wave per 64/S instances (N <= 64), or one workgroup of
@@ -17,7 +18,6 @@
 
 #include <dlfcn.h>
 #include <unistd.h>
-#include <rccl/rccl.h>                 // types only: librccl is opened at bftsim_comm_init (dlopen)
 #include <hipcub/hipcub.hpp>
 
 #include <mutex>
@@ -25,17 +25,10 @@
 #include <utility>
 #include <vector>
 
-#include "bft_hip.h"
+#include "bftsim_impl.h"
 #include "bft_fast64.h"
 #include "bft_crypto.h"
-#include "bft_trace.h"
 #include "bft_twins.h"
-#include "bft_audit.h"
-#include "bft_archive.h"
-#include "bft_accuse.h"
-#include "bft_timeline.h"
-#include "bft_rollcall.h"
-#include "bft_ledger.h"
 
 namespace bft {
 
@@ -315,27 +308,6 @@ __global__ __launch_bounds__(64) void bft_export_votes_kernel(Params p, const ui
 // ------------------------------------------------------------------------------ the trace (SPEC.md §11b)
 // The signed wire frame of every logged broadcast (bftsim_export_trace), from what bftsim_crypto_verify kept:
 // a size pass (lane per message, the frame emitter of bft_trace.h with a counting functor), a scan, an emit pass.
-struct TraceArgs {
-    const uint32_t* mlog;
-    uint32_t cap;
-    // dense, per message: kept by bftsim_crypto_verify (bftsim_set_trace_keep)
-    const uint64_t* moff;             // [n_inst + 1]
-    const uint64_t* mref;
-    const uint8_t* raw;
-    const uint32_t* msg_k;
-    const uint8_t* sigs;
-    const uint8_t* seals;
-};
-// twins (bftsim_set_trace_twins, SPEC.md §11f): the merged frame index and, per twin slot, what TraceArgs' dense arrays
-// hold per message. An argument of the twin kernels alone (TwinOpt)
-struct TwinArgs {
-    const uint64_t* fmap;             // [frames] message, | twins::F_TWIN for a twin
-    const uint32_t* tslot;            // [messages + 1] twins before message m: a twin's slot
-    const uint8_t* traw;
-    const uint32_t* tmsg_k;
-    const uint8_t* tsigs;
-    const uint8_t* tseals;
-};
 // the last argument of a trace kernel: nothing for a trace without twins, whose kernels so keep their arguments
 template <bool TW> struct TwinOpt {};
 template <> struct TwinOpt<true> { TwinArgs a; };
@@ -512,217 +484,6 @@ __global__ __launch_bounds__(256) void bft_l2_evict_kernel(const uint4* buf, uin
     if (acc == 0x9e3779b9u) *sink = acc;              // keeps the loads; the buffer is zero, so never taken
 }
 
-struct bftsim {
-    bftsim_config cfg;
-    std::vector<uint8_t> addresses;
-    int device = 0;
-    std::string err;
-    uint8_t genesis_hash[32];
-    uint32_t genesis_seed = 0;
-    uint32_t seg = 64;
-    uint32_t hcap = 0;
-    // device buffers
-    uint64_t cap_inst = 0;
-    uint8_t* d_addr = nullptr;
-    uint8_t* d_ghash = nullptr;
-    uint32_t* d_ch = nullptr;
-    uint32_t* d_flags = nullptr;
-    uint32_t* d_ticks = nullptr;
-    uint64_t* d_views = nullptr;
-    uint32_t* d_rec = nullptr;
-    uint8_t* d_hash = nullptr;
-    unsigned long long* d_stats = nullptr;
-    uint64_t* d_hist = nullptr;       // [HIST_BINS] of the last launch
-    uint64_t* d_red = nullptr;        // bftsim_stats image reduced by bftsim_stats_allreduce
-    uint4* d_evict = nullptr;         // attribution pass only (bft_l2_evict_kernel): 64 MiB of zeros
-    bool pmc_evict = false;
-    ncclComm_t comm = nullptr;        // bftsim_comm_init: one rank of a multi-GPU run (RCCL over xGMI)
-    // real-crypto mode (bftsim_set_crypto, SPEC.md §11)
-    bool crypto = false;
-    uint64_t forged[4] = {0, 0, 0, 0};
-    uint32_t mlog_cap = 0;
-    uint32_t* d_mlog = nullptr;       // [cap_inst][mlog_cap][MLOG_WORDS]
-    uint32_t* d_mlog_n = nullptr;     // [cap_inst]
-    uint8_t* d_keys = nullptr;        // [2N][32]: the validators' secrets, then their forged keys
-    uint32_t* d_vsnap = nullptr;      // [cap_inst][seg][8] commit set at each lane's last commit
-    uint32_t* d_votes = nullptr;      // [cap_inst][rows][8] canonical committer's commit set per height
-    uint8_t* d_vsig = nullptr;        // [last_n][H][N][65] the votes' signatures, or their seals (bftsim_crypto_verify)
-    uint8_t* d_vhas = nullptr;        // [last_n][H][N]
-    uint64_t vsig_n = 0;              // instances d_vsig holds (0: no verify since the last launch)
-    uint32_t ledger_votes = BFTSIM_VOTES_SIGNATURES;   // what the next verify gathers (bftsim_set_ledger_votes)
-    void* sig = nullptr;              // libbftsig handle (bftsig_t*)
-    // the trace (bftsim_set_trace_keep, SPEC.md §11b): what bftsim_crypto_verify kept of the last launch
-    bool trace_keep = false;
-    uint8_t* d_tkeep = nullptr;       // one allocation: moff, mref, raw, msg_k, sigs, seals (trace_args points into it)
-    bft::TraceArgs trace_args{};
-    bft::TwinArgs twin_args{};
-    uint64_t trace_n = 0, trace_M = 0;    // instances (0: nothing kept) and messages it holds
-    uint64_t* d_tfoff = nullptr;      // [M + 1] frame offsets, then [n + 1] instance offsets, then the error counter
-    std::vector<uint64_t> trace_moff, trace_ioff;   // host, [n + 1]: first frame / first stream byte of each instance
-    float trace_ms[3] = {0, 0, 0};    // size pass + scan, emit kernel, device-to-host copies of the last calls
-    // twins (bftsim_set_trace_twins, SPEC.md §11f): the kept trace's frames are its messages and their twins
-    bool trace_twins = false;         // what the next keeping verify does
-    bool trace_has_twins = false;     // the kept trace was built with twins on
-    uint8_t* d_twkeep = nullptr;      // one allocation: tslot, if0, fmap, traw, tmsg_k, tsigs, tseals (trace_args points into it)
-    const uint64_t* d_tif0 = nullptr; // [n + 1] first frame of each instance (twins off: trace_args.moff)
-    uint64_t trace_F = 0;             // frames: trace_M + the twins
-    uint64_t twin_counts[2] = {0, 0}; // PrePrepare twins, vote twins of the kept trace
-    float twin_ms[3] = {0, 0, 0};     // mark + scan + merge, digests, signing of the last verify with twins on
-    float audit_ms[4] = {0, 0, 0, 0}; // decode, recoveries, classify + tally, copies of the last audit (SPEC.md §11c)
-    float ledger_ms[4] = {0, 0, 0, 0};// decode, recoveries, tally + link, copies of the last bftsim_verify_ledger (§11d)
-    uint8_t* d_tips = nullptr;        // [cap_inst * 32]
-    uint32_t* d_rcs = nullptr;        // RoundChangeSet tables, rcs_words(seg) per wave / workgroup
-    uint32_t* d_backlog = nullptr;    // replay mode: backlog slots, backlog_words(seg) per wave / workgroup
-    uint64_t backlog_bytes = 0;
-    uint32_t* d_resume = nullptr;     // FAST launches: [cap_inst] hand-over flags
-    uint32_t* d_resume_q = nullptr;   // FAST launches: [2 + cap_inst] the resume kernel's queue
-    uint32_t* d_save = nullptr;       // FAST launches: [SAVE_WORDS][cap_inst * 64] saved lane state
-    int fast = 1;                     // FAST kernel + resume for N = 64 (bftsim_set_fast(h, 0): full kernel)
-    uint32_t window = 0;              // 0: full per-height rows; else ring of `window` rows
-    uint32_t rcs_k = bft::RCS_DEFAULT_K;   // RoundChangeSet rounds per validator (bftsim_set_rcs_capacity)
-    uint64_t* d_trace = nullptr;
-    uint64_t* h_trace = nullptr;
-    uint32_t trace_ticks = 0;
-    uint64_t n_req = 0;               // instances of the next launch (bftsim_prepare); <= cap_inst
-    uint64_t last_n = 0, last_first = 0;
-    hipStream_t last_stream = nullptr;
-    // Pipelined launches (bftsim_set_pipeline(h, D), the batch-throughput mode): a ring of D row-table sets,
-    // each with the scratch of one launch, so that up to D launches are in flight at once.
-    //   * the consensus kernel (+ resume + suffix rows) of each launch runs on one of `n_cs` launch streams
-    //     (round-robin), after the caller's earlier work on its stream and after its set's last chain;
-    //   * the prev_hash chains of `hash_batch` consecutive launches run as ONE chain kernel on one of `n_hs`
-    //     hash streams (round-robin). A chain is sequential in height and a launch's chains take ~1.5 ms
-    //     whatever their number, so batching B launches per kernel gives B times the chain throughput
-    //     (profiles/r04). Results are complete once bftsim_sync (or any fetch) returns; those flush a
-    //     partial batch first.
-    static constexpr uint32_t MAX_SETS = 32, MAX_CS = 8, MAX_HS = 8, MAX_BATCH = bft::CHAIN_MAX_SETS;
-    struct RowSet {
-        uint32_t* ch = nullptr; uint32_t* flags = nullptr; uint32_t* ticks = nullptr; uint64_t* views = nullptr;
-        uint32_t* rec = nullptr; uint8_t* hash = nullptr;
-        uint32_t* sfx = nullptr;      // header suffix rows of the hash pass (sfx_rows per instance)
-        uint32_t* spec = nullptr;     // little-endian seeds, N = 64: predicted blocks [H + 1][n] (seed chain)
-        // big-endian seeds, N = 64: predicted chains: Byzantine masks [n], first height whose
-        // recorded block differs from its prediction [n]
-        uint64_t* byz = nullptr; uint32_t* bad = nullptr;
-        uint32_t* pred = nullptr;     // [n][H] the predicted block of each height (bft_spec_suffix_kernel)
-        // a launch's own scratch (set 0: the handle's buffers)
-        uint64_t* hist = nullptr; uint32_t* rcs = nullptr; uint32_t* backlog = nullptr;
-        uint32_t* resume = nullptr; uint32_t* save = nullptr; uint32_t* resume_q = nullptr;
-        uint32_t* hint = nullptr;     // host-mapped: the hand-over count of the set's last launch (resume grid)
-        hipEvent_t done = nullptr;    // hash pass of the last launch that used the set
-        hipEvent_t batch_done = nullptr;   // or: the event of the chain batch that hashed it (flush_batch)
-        hipEvent_t entry = nullptr;   // the caller's stream at the launch call
-        bool busy = false;
-    } sets[MAX_SETS];
-    // block-hash chains: one wave per instance (bft_hash_chain_wave_kernel) up to this many instances per
-    // launch, lane pairs above. 0: lane pairs at every size -- the wave chain measured slower at every
-    // shard size (ds_bpermute latency and LDS issue at low occupancy), kept as an A/B arm
-    // (BFTSIM_TESTING + BFTSIM_CHAIN_WAVE_MAX)
-    uint64_t chain_wave_max = 0;
-    // one lane per instance from this many instances per launch (kern_fast.hip bft_hash_chain_lane_kernel: fewer
-    // instructions per header, longer chains; BFTSIM_TESTING + BFTSIM_CHAIN_LANE_MIN overrides)
-    // predicted lanes against predicted lane pairs (r06/ab_mid, ab_lane_min): 8,192 1.69e9-1.70e9 vs 1.47e9-1.49e9;
-    // 6,144 1.52e9-1.59e9 vs 1.45e9-1.46e9; 5,120 1.36e9 vs 1.41e9; 4,096 1.31e9 vs 1.41e9
-    uint64_t chain_lane_min = 6144;
-    // persistent lane-chain waves per dispatch, 0: a wave per 64 instances (BFTSIM_TESTING + BFTSIM_CHAIN_GRID; an A/B
-    // arm: capping the chain waves so that the consensus kernels keep SIMD slots measured the same or slower)
-    uint32_t chain_grid = 0;
-    // lane chains encode each height's suffix themselves from the recorded rows: no suffix-row kernel on the launch
-    // streams (0.3-0.45 ms per cfg3 launch beside the FAST kernels), no 400 MB of rows written and read back
-    // (BFTSIM_TESTING + BFTSIM_CHAIN_INLINE=0: the suffix rows)
-    uint32_t chain_inline = 1;
-    // s_setprio of the chain waves (Params::chain_prio), against the FAST kernels' 2. Recorded chains: 0. Predicted
-    // lane pairs (small shards, their latency the step's tail) above the FAST kernels, with their suffix rows, at the
-    // sync's flush and at earlier ones alike: 2,048 per GPU 1.08e9 at 0, 1.13e9-1.22e9 at 3 (profiles/r06/ab_prio).
-    // Predicted lanes (large shards: throughput, not latency) below them: cfg3 2.06e9-2.10e9 at 0 or 1 against
-    // 1.80e9-1.93e9 at 3 (profiles/r06/ab_spec_lane).
-    static constexpr uint32_t PRIO_RECORDED = 0, PRIO_SPEC_PAIR = 3, PRIO_SPEC_LANE = 0;
-    bool seed_spec = true;            // little-endian seeds, N = 64: predicted blocks (BFTSIM_TESTING + BFTSIM_SEED_SPEC=0: off)
-    int pipeline = 0;                 // number of row-table sets (0: no pipelining)
-    uint32_t sfx_rows = 0;            // heights per hash-pass chunk (0: no hash pass)
-    uint32_t n_sets = 0, cur_set = 0;
-    bool last_pipe = false;           // the last launch ran on the launch streams
-    hipStream_t cs[MAX_CS] = {}, hstr[MAX_HS] = {};
-    uint32_t n_cs = 2, n_hs = 2, cur_cs = 0, cur_hs = 0;
-    // launch streams with little-endian seeds: a launch's seed chain and FAST kernel are serial on its stream
-    // and there is no hash pass, so more launches run side by side (profiles/r04/ab_le_streams)
-    static constexpr uint32_t N_CS_SEEDED = 4;
-    uint32_t hash_batch = 4;          // launches per chain kernel (BFTSIM_TESTING + BFTSIM_HASH_BATCH overrides)
-    // big-endian seeds, N = 64, pipelined: the chains of a batch run on predicted blocks from launch time on
-    // (BFTSIM_TESTING + BFTSIM_HASH_SPEC=0: off), over up to N_HS_SPEC hash streams so that the
-    // batches of a burst of launches run side by side
-    // on at every size: a small shard's chains (lane pairs) are bound by their latency, which they start ahead
-    // of; a large shard's (lanes, each predicting and encoding its blocks itself) fill the issue slots the consensus
-    // kernels leave from the first launch on (cfg3: 2.06e9-2.10e9 against 1.94e9-1.98e9 recorded;
-    // profiles/r06/ab_spec_lane). BFTSIM_TESTING + BFTSIM_HASH_SPEC=0: recorded chains at every size; =2: predicted
-    // for lossy schedules too
-    uint64_t hash_spec_max = ~0ull;
-    bool spec_lossy = false;          // predicted chains with drops or crashes too (BFTSIM_HASH_SPEC=2)
-    static constexpr uint32_t N_HS_SPEC = 3;
-    struct Pending { uint32_t set, ev, first, cs; } pend[MAX_BATCH];   // cs: the launch stream it ran on
-    // one event per chain batch (flush_batch) instead of one per set: a ring, re-recorded after BATCH_EVS batches. Safe
-    // because BATCH_EVS > MAX_SETS: a batch marks at least one set, so more than MAX_SETS batches cannot all still be
-    // some set's batch_done; by the time an event is re-recorded no set points at it
-    static constexpr uint32_t BATCH_EVS = 64;
-    static_assert(BATCH_EVS > MAX_SETS, "a re-recorded batch event must not be any set's batch_done");
-    hipEvent_t batch_ev[BATCH_EVS] = {};
-    uint32_t batch_ev_head = 0;
-    uint32_t n_pend = 0;
-    bft::Params batch_p{};            // the launch parameters of the pending batch (sizes, genesis, prio)
-    bool batch_spec = false;          // the pending batch runs predicted chains
-    uint32_t batch_hs = 0;            // the pending batch's hash stream (chosen at its first launch)
-    // per-launch kernel timing: a ring of event quadruples, read by bftsim_kernel_ms_sum
-    static constexpr uint32_t RING = 64;
-    struct LaunchEv { hipEvent_t c0, c1, h0, h1, sx; bool has_hash, pending; } ring[RING] = {};
-    uint32_t ring_head = 0;
-    double acc_c = 0, acc_h = 0;
-    uint32_t acc_n = 0;
-    float archive_ms[4] = {0, 0, 0, 0};// the observer's passes, pick, emit + heights, copies of the last archive (SPEC.md §11e)
-    float accuse_ms[4] = {0, 0, 0, 0}; // the observer's passes, walk, mark + scan + gather, copies of the last accuse (SPEC.md §11g)
-    float timeline_ms[4] = {0, 0, 0, 0};// the observer's passes, walk, rows, copies of the last timeline (SPEC.md §11h)
-    float rollcall_ms[6] = {0, 0, 0, 0, 0, 0};   // the observer's, the chronicler's, views, walk, scan + gather, copies (§11i)
-};
-
-static int fail(bftsim* h, int code, const std::string& msg) {
-    if (h) h->err = msg;
-    return code;
-}
-#define HIPCHECK(h, x)                                                                          \
-    do {                                                                                        \
-        hipError_t e_ = (x);                                                                    \
-        if (e_ != hipSuccess) return fail(h, BFTSIM_EHIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-// Owners of the cold paths' temporaries (verify, export, audit): released on every return, so that each HIP call
-// there is a HIPCHECK with an early return. Not for the launch path, which owns nothing temporary.
-namespace {                           // internal: the library exports none of their members
-struct DevMem {                       // a device allocation
-    void* p = nullptr;
-    DevMem() = default;
-    DevMem(DevMem&& o) noexcept : p(o.release<void>()) {}
-    DevMem(const DevMem&) = delete;
-    DevMem& operator=(const DevMem&) = delete;
-    ~DevMem() { (void)hipFree(p); }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes); }
-    template <class T> T* as() const { return (T*)p; }
-    template <class T> T* release() { T* r = (T*)p; p = nullptr; return r; }   // the handle takes the allocation over
-};
-struct Events {                       // up to MAX timing events
-    static constexpr int MAX = 6;
-    hipEvent_t ev[MAX] = {};
-    Events() = default;
-    Events(const Events&) = delete;
-    Events& operator=(const Events&) = delete;
-    ~Events() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
-    hipError_t create(int n) {
-        for (int k = 0; k < n && k < MAX; ++k)
-            if (hipError_t e = hipEventCreate(&ev[k]); e != hipSuccess) return e;
-        return hipSuccess;
-    }
-    hipEvent_t operator[](int k) const { return ev[k]; }
-};
-}  // namespace
-
 // the attribution pass's eviction after a kernel (a no-op unless BFTSIM_TESTING=1 and BFTSIM_PMC_EVICT=1)
 static constexpr uint64_t EVICT_BYTES = 64ull << 20;
 static hipError_t pmc_evict(bftsim* h, hipStream_t s) {
@@ -869,18 +630,10 @@ void comm_destroy(ncclComm_t c) {
     if (rccl().ok) (void)rccl().destroy(c);
 }
 
-// libbftsig (include/bftsig.h), next to this library: the batched secp256k1 of real-crypto mode
-struct SigApi {
-    int (*create)(int, void**) = nullptr;
-    void (*destroy)(void*) = nullptr;
-    const char* (*last_error)(const void*) = nullptr;
-    int (*secret_to_address)(void*, const uint8_t*, uint64_t, uint8_t*, uint8_t*, uint8_t*, void*) = nullptr;
-    int (*sign)(void*, const uint8_t*, const uint32_t*, const uint8_t*, uint64_t, uint8_t*, uint8_t*, void*) = nullptr;
-    int (*recover)(void*, const uint8_t*, const uint8_t*, uint64_t, uint8_t*, uint8_t*, uint8_t*, void*) = nullptr;
-    bool ok = false;
-    std::string why;
-};
-void sig_api_anchor() {}
+}  // namespace
+
+// libbftsig (include/bftsig.h), next to this library, opened on first use (SigApi: bftsim_impl.h)
+static void sig_api_anchor() {}
 SigApi& sig_api() {
     static SigApi a;
     static std::once_flag once;
@@ -905,7 +658,6 @@ SigApi& sig_api() {
     });
     return a;
 }
-}  // namespace
 
 extern "C" {
 
@@ -2110,7 +1862,10 @@ int bftsim_set_trace_keep(bftsim_t* h, int on) {
     return BFTSIM_OK;
 }
 
-static int trace_ready(bftsim* h, const char* what) {
+}  // extern "C"
+
+// the kept trace's passes, which the analysers' *_last_trace entry points run too (declared in bftsim_impl.h)
+int trace_ready(bftsim* h, const char* what) {
     if (!h->crypto) return fail(h, BFTSIM_EINVAL, std::string(what) + ": bftsim_set_crypto not called");
     if (!h->trace_keep) return fail(h, BFTSIM_EINVAL, std::string(what) + ": bftsim_set_trace_keep is off");
     if (h->trace_n == 0 || h->trace_n != h->last_n)
@@ -2119,7 +1874,7 @@ static int trace_ready(bftsim* h, const char* what) {
 }
 
 // size pass + scan over every kept message, once per verify: d_tfoff and the host's per-instance offsets
-static int trace_size_pass(bftsim* h) {
+int trace_size_pass(bftsim* h) {
     if (h->d_tfoff) return BFTSIM_OK;
     const uint64_t n = h->trace_n, M = h->trace_F;               // every frame: the messages and their twins
     if (M + 1 > 0x7fffffffull) return fail(h, BFTSIM_EINVAL, "trace: too many messages for one scan");
@@ -2159,7 +1914,7 @@ static int trace_size_pass(bftsim* h) {
 
 // emit pass: frames [m0, m1) of the kept trace (messages, and their twins where it has them) into d_out, complete when it returns. The two passes must agree on
 // every frame's length; `what` names the caller in the error. t0 / t1 (or null): recorded around the kernel alone.
-static int trace_emit(bftsim* h, const char* what, uint64_t m0, uint64_t m1, uint8_t* d_out, hipEvent_t t0,
+int trace_emit(bftsim* h, const char* what, uint64_t m0, uint64_t m1, uint8_t* d_out, hipEvent_t t0,
                       hipEvent_t t1) {
     hipStream_t s = h->last_stream;
     uint32_t* d_err = (uint32_t*)(h->d_tfoff + h->trace_F + 1 + h->trace_n + 1);
@@ -2184,6 +1939,8 @@ static int trace_emit(bftsim* h, const char* what, uint64_t m0, uint64_t m1, uin
                                         " frames whose emitted length differs from the counted one");
     return BFTSIM_OK;
 }
+
+extern "C" {
 
 int bftsim_trace_sizes(bftsim_t* h, uint64_t capacity, uint32_t* inst_frames, uint64_t* inst_bytes) {
     if (!h) return BFTSIM_EINVAL;
@@ -2250,11 +2007,7 @@ int bftsim_export_trace(bftsim_t* h, uint64_t inst_begin, uint64_t inst_count, u
 }
 
 int bftsim_trace_last_ms(bftsim_t* h, float* size_ms, float* emit_ms, float* copy_ms) {
-    if (!h) return BFTSIM_EINVAL;
-    if (size_ms) *size_ms = h->trace_ms[0];
-    if (emit_ms) *emit_ms = h->trace_ms[1];
-    if (copy_ms) *copy_ms = h->trace_ms[2];
-    return BFTSIM_OK;
+    return h ? last_ms(h->trace_ms, {size_ms, emit_ms, copy_ms}) : BFTSIM_EINVAL;
 }
 
 // ---- twins (SPEC.md §11f)
@@ -2274,925 +2027,7 @@ int bftsim_trace_twin_counts(bftsim_t* h, uint64_t* pp_twins, uint64_t* vote_twi
 }
 
 int bftsim_trace_twins_last_ms(bftsim_t* h, float* index_ms, float* digest_ms, float* sign_ms) {
-    if (!h) return BFTSIM_EINVAL;
-    if (index_ms) *index_ms = h->twin_ms[0];
-    if (digest_ms) *digest_ms = h->twin_ms[1];
-    if (sign_ms) *sign_ms = h->twin_ms[2];
-    return BFTSIM_OK;
-}
-
-// ---- the observer (SPEC.md §11c): decode, recoveries, classification and tally of a frame stream on the device
-// libbftsig, opened as bftsim_set_crypto opens it; the observer needs no secrets
-static int audit_sig(bftsim* h) {
-    SigApi& a = sig_api();
-    if (!a.ok) return fail(h, BFTSIM_EUNSUPPORTED, a.why);
-    if (!h->sig && a.create(h->device, &h->sig) != 0) return fail(h, BFTSIM_EHIP, "bftsig_create failed");
-    return BFTSIM_OK;
-}
-// ---- the archiver (SPEC.md §11e): a continuation of audit_device, run after the tally while the pool is alive. Its
-// tables and header slots are one more piece of the pool; the observer's two entry points pass none.
-namespace {
-struct ArchiveCont {
-    uint8_t* hdr;                     // the caller's
-    uint64_t slot_bytes;
-    uint32_t* hdr_len;
-    const bftsim_archive_out* out;
-    bftsim_archive_report* report;
-    // the piece's layout (archive_layout): the device slot is the smallest the boundary admits
-    uint64_t dslot, bytes, o_pick, o_hdr, o_len, o_status, o_pp, o_nv, o_nf, o_height, o_counts;
-    unsigned long long counts[bft::archive::CNT_WORDS];
-    float ms[2];                      // pick, emit + heights
-};
-}  // namespace
-static int archive_layout(bftsim* h, ArchiveCont& ac, uint64_t inst, uint32_t max_heights) {
-    namespace R = bft::archive;
-    const uint64_t rows = inst * max_heights, Rx = rows ? rows : 1, Ix = inst ? inst : 1;
-    if (rows >= (1ull << 31) - 1) return fail(h, BFTSIM_ENOMEM, "bftsim_archive: 2^31 header slots or more");
-    ac.dslot = bftsim_ledger_slot_bytes(h->cfg.n);
-    uint64_t bytes = 0;
-    auto sized = [&](uint64_t b) { const uint64_t o = bytes; bytes += (b + 31) & ~31ull; return o; };
-    ac.o_pick = sized(Rx * R::pick_words(bftsim_two_thirds_majority(h->cfg.n)) * 4);
-    ac.o_hdr = sized(Rx * ac.dslot);
-    ac.o_len = sized(Rx * 4); ac.o_status = sized(Rx); ac.o_pp = sized(Rx * 4); ac.o_nv = sized(Rx * 2); ac.o_nf = sized(Rx * 2);
-    ac.o_height = sized(Ix * 8); ac.o_counts = sized(R::CNT_WORDS * 8);
-    ac.bytes = bytes;
-    return BFTSIM_OK;
-}
-static int archive_passes(bftsim* h, ArchiveCont& ac, uint8_t* p, const uint8_t* d_stream, const uint64_t* d_foff, uint64_t base,
-                          uint64_t frames, const bft::audit::Recs& r, const uint8_t* d_status, const int32_t* d_signer,
-                          const uint64_t* d_if0, uint64_t inst, uint32_t max_heights, const bft::archive::Certs& certs,
-                          hipStream_t s) {
-    namespace R = bft::archive;
-    const R::Args a{d_stream, d_foff, base, frames, r, d_status, d_signer, d_if0, inst, max_heights,
-                    bftsim_two_thirds_majority(h->cfg.n), certs, (uint32_t*)(p + ac.o_pick), p + ac.o_hdr, ac.dslot,
-                    (uint32_t*)(p + ac.o_len), p + ac.o_status, (uint32_t*)(p + ac.o_pp), (uint16_t*)(p + ac.o_nv),
-                    (uint16_t*)(p + ac.o_nf), (uint64_t*)(p + ac.o_height), (unsigned long long*)(p + ac.o_counts)};
-    Events ev;
-    HIPCHECK(h, ev.create(3));
-    HIPCHECK(h, hipMemsetAsync(p + ac.o_pick, 0xff, ac.o_hdr - ac.o_pick, s));        // NONE
-    HIPCHECK(h, hipMemsetAsync(p + ac.o_hdr, 0, ac.bytes - ac.o_hdr, s));             // the slots' tails, the counters
-    HIPCHECK(h, hipEventRecord(ev[0], s));
-    HIPCHECK(h, R::launch_pick(a, s));
-    HIPCHECK(h, hipEventRecord(ev[1], s));
-    HIPCHECK(h, R::launch_emit(a, s));
-    HIPCHECK(h, R::launch_heights(a, s));
-    HIPCHECK(h, hipEventRecord(ev[2], s));
-    HIPCHECK(h, hipMemcpyAsync(ac.counts, p + ac.o_counts, sizeof ac.counts, hipMemcpyDeviceToHost, s));
-    HIPCHECK(h, hipStreamSynchronize(s));
-    for (int k = 0; k < 2; ++k) HIPCHECK(h, hipEventElapsedTime(&ac.ms[k], ev[k], ev[k + 1]));
-    if (ac.counts[R::CNT_ERR])     // a header above its slot, or an emit pass that disagrees with the pick pass
-        return fail(h, BFTSIM_EHIP, "bftsim_archive: " + std::to_string(ac.counts[R::CNT_ERR]) +
-                                        " headers did not fit their slot or lost a picked frame");
-    return BFTSIM_OK;
-}
-static int archive_copy(bftsim* h, ArchiveCont& ac, const uint8_t* p, uint64_t inst, uint32_t max_heights, hipStream_t s) {
-    namespace R = bft::archive;
-    const uint64_t rows = inst * max_heights;
-    Events ev;
-    HIPCHECK(h, ev.create(2));
-    HIPCHECK(h, hipEventRecord(ev[0], s));
-    if (rows) {
-        HIPCHECK(h, hipMemcpy2DAsync(ac.hdr, ac.slot_bytes, p + ac.o_hdr, ac.dslot, ac.dslot, rows, hipMemcpyDeviceToHost, s));
-        HIPCHECK(h, hipMemcpyAsync(ac.hdr_len, p + ac.o_len, rows * 4, hipMemcpyDeviceToHost, s));
-    }
-    if (ac.out) {
-        const struct { void* dst; uint64_t off, b; } back[] = {
-            {ac.out->status, ac.o_status, rows}, {ac.out->pp_frame, ac.o_pp, rows * 4}, {ac.out->n_votes, ac.o_nv, rows * 2},
-            {ac.out->archived_height, ac.o_height, inst * 8}};
-        for (const auto& k : back)
-            if (k.dst && k.b) HIPCHECK(h, hipMemcpyAsync(k.dst, p + k.off, k.b, hipMemcpyDeviceToHost, s));
-    }
-    HIPCHECK(h, hipEventRecord(ev[1], s));
-    HIPCHECK(h, hipStreamSynchronize(s));
-    float copy_ms = 0;
-    HIPCHECK(h, hipEventElapsedTime(&copy_ms, ev[0], ev[1]));
-    h->archive_ms[0] = h->audit_ms[0] + h->audit_ms[1] + h->audit_ms[2];
-    h->archive_ms[1] = ac.ms[0]; h->archive_ms[2] = ac.ms[1]; h->archive_ms[3] = h->audit_ms[3] + copy_ms;
-    bftsim_archive_report* rep = ac.report;
-    memset(rep, 0, sizeof *rep);
-    rep->headers = ac.counts[R::CNT_STATUS + R::AR_OK];
-    for (int k = 0; k < 3; ++k) rep->by_status[k] = ac.counts[R::CNT_STATUS + k];
-    rep->votes = ac.counts[R::CNT_VOTES];
-    rep->foreign_seals = ac.counts[R::CNT_FOREIGN];
-    rep->archived_instances = ac.counts[R::CNT_ARCHIVED];
-    return BFTSIM_OK;
-}
-// ---- the accuser (SPEC.md §11g): a continuation of audit_device like the archiver's, run after the classify and
-// tally passes over their records, statuses and signers, which it only reads. Its tables are one more piece of the pool.
-namespace {
-struct AccuseCont {
-    uint32_t view_cap;
-    const bftsim_accuse_out* out;     // the caller's
-    bftsim_accuse_report* report;
-    uint64_t rec_cap, bytes, o_views, o_first, o_pair, o_acc, o_flags, o_mark, o_pos, o_recs, o_counts, o_scan;
-    size_t scan_bytes;
-    unsigned long long counts[bft::accuse::CNT_WORDS];
-    uint32_t total;                   // the scan's
-    float ms[2];                      // walk, mark + scan + gather
-};
-}  // namespace
-static int accuse_layout(bftsim* h, AccuseCont& xc, uint64_t frames, uint64_t inst, uint32_t max_heights) {
-    namespace X = bft::accuse;
-    const uint64_t Fx = frames ? frames : 1, Ix = inst ? inst : 1;
-    if (xc.view_cap == 0) xc.view_cap = X::default_view_cap(max_heights);
-    const uint64_t per_view = sizeof(X::View) + 12ull * h->cfg.n;
-    if (xc.view_cap > (1ull << 40) / per_view / Ix)
-        return fail(h, BFTSIM_ENOMEM, "bftsim_accuse: view_cap x instances above 1 TiB of view tables");
-    if (frames >= (1ull << 31) - 1) return fail(h, BFTSIM_ENOMEM, "bftsim_accuse: 2^31 frames or more");    // the scan's int
-    xc.rec_cap = xc.out->records ? (xc.out->rec_cap < frames ? xc.out->rec_cap : frames) : 0;   // a frame closes one record at most
-    uint64_t bytes = 0;
-    auto sized = [&](uint64_t b) { const uint64_t o = bytes; bytes += (b + 31) & ~31ull; return o; };
-    xc.o_views = sized(Ix * xc.view_cap * sizeof(X::View));
-    xc.o_first = sized(Ix * xc.view_cap * 12ull * h->cfg.n);
-    xc.o_pair = sized(Fx * 4);
-    xc.o_acc = sized(Ix * 32); xc.o_flags = sized(Ix * 4);
-    xc.o_mark = sized((Fx + 1) * 4); xc.o_pos = sized((Fx + 1) * 4);
-    xc.o_recs = sized((xc.rec_cap ? xc.rec_cap : 1) * sizeof(X::Record));
-    xc.o_counts = sized(X::CNT_WORDS * 8);
-    xc.scan_bytes = 0;
-    HIPCHECK(h, hipcub::DeviceScan::ExclusiveSum(nullptr, xc.scan_bytes, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)(frames + 1)));
-    xc.o_scan = sized(xc.scan_bytes ? xc.scan_bytes : 1);
-    xc.bytes = bytes;
-    return BFTSIM_OK;
-}
-static int accuse_passes(bftsim* h, AccuseCont& xc, uint8_t* p, uint64_t frames, const bft::audit::Recs& r,
-                         const uint8_t* d_status, const int32_t* d_signer, const uint64_t* d_if0, uint64_t inst, hipStream_t s) {
-    namespace X = bft::accuse;
-    const X::Args a{r, d_status, d_signer, d_if0, frames, inst, h->cfg.n, xc.view_cap, (X::View*)(p + xc.o_views),
-                    (uint32_t*)(p + xc.o_first), (uint32_t*)(p + xc.o_pair), (uint64_t*)(p + xc.o_acc),
-                    (uint32_t*)(p + xc.o_flags), (uint32_t*)(p + xc.o_mark), (uint32_t*)(p + xc.o_pos),
-                    (X::Record*)(p + xc.o_recs), xc.rec_cap, (unsigned long long*)(p + xc.o_counts)};
-    Events ev;
-    HIPCHECK(h, ev.create(3));
-    HIPCHECK(h, hipMemsetAsync(p + xc.o_first, 0xff, xc.o_acc - xc.o_first, s));      // NONE: first and frame_pair
-    HIPCHECK(h, hipMemsetAsync(p + xc.o_acc, 0, xc.o_mark - xc.o_acc, s));            // instances without a wave
-    HIPCHECK(h, hipMemsetAsync(p + xc.o_counts, 0, X::CNT_WORDS * 8, s));
-    HIPCHECK(h, hipEventRecord(ev[0], s));
-    HIPCHECK(h, X::launch_walk(a, s));
-    HIPCHECK(h, hipEventRecord(ev[1], s));
-    HIPCHECK(h, X::launch_mark(a, s));
-    HIPCHECK(h, hipcub::DeviceScan::ExclusiveSum(p + xc.o_scan, xc.scan_bytes, a.mark, a.pos, (int)(frames + 1), s));
-    HIPCHECK(h, X::launch_gather(a, s));
-    HIPCHECK(h, hipEventRecord(ev[2], s));
-    HIPCHECK(h, hipMemcpyAsync(xc.counts, p + xc.o_counts, sizeof xc.counts, hipMemcpyDeviceToHost, s));
-    HIPCHECK(h, hipMemcpyAsync(&xc.total, a.pos + frames, 4, hipMemcpyDeviceToHost, s));
-    HIPCHECK(h, hipStreamSynchronize(s));
-    for (int k = 0; k < 2; ++k) HIPCHECK(h, hipEventElapsedTime(&xc.ms[k], ev[k], ev[k + 1]));
-    if (xc.total != xc.counts[X::CNT_RECORDS])
-        return fail(h, BFTSIM_EHIP, "bftsim_accuse: the scan's total disagrees with the walk's count");
-    return BFTSIM_OK;
-}
-static int accuse_copy(bftsim* h, AccuseCont& xc, const uint8_t* p, uint64_t frames, uint64_t inst, hipStream_t s) {
-    namespace X = bft::accuse;
-    const uint64_t written = xc.total < xc.rec_cap ? xc.total : xc.rec_cap;
-    Events ev;
-    HIPCHECK(h, ev.create(2));
-    HIPCHECK(h, hipEventRecord(ev[0], s));
-    const struct { void* dst; uint64_t off, b; } back[] = {
-        {xc.out->frame_pair, xc.o_pair, frames * 4}, {xc.out->inst_accused, xc.o_acc, inst * 32},
-        {xc.out->inst_flags, xc.o_flags, inst * 4}, {xc.out->records, xc.o_recs, written * sizeof(X::Record)}};
-    for (const auto& k : back)
-        if (k.dst && k.b) HIPCHECK(h, hipMemcpyAsync(k.dst, p + k.off, k.b, hipMemcpyDeviceToHost, s));
-    HIPCHECK(h, hipEventRecord(ev[1], s));
-    HIPCHECK(h, hipStreamSynchronize(s));
-    float copy_ms = 0;
-    HIPCHECK(h, hipEventElapsedTime(&copy_ms, ev[0], ev[1]));
-    h->accuse_ms[0] = h->audit_ms[0] + h->audit_ms[1] + h->audit_ms[2];
-    h->accuse_ms[1] = xc.ms[0]; h->accuse_ms[2] = xc.ms[1]; h->accuse_ms[3] = h->audit_ms[3] + copy_ms;
-    bftsim_accuse_report* rep = xc.report;
-    memset(rep, 0, sizeof *rep);
-    rep->records = xc.counts[X::CNT_RECORDS];
-    for (int k = 0; k < 3; ++k) rep->by_code[k] = xc.counts[X::CNT_CODE + k];
-    rep->accused = xc.counts[X::CNT_ACCUSED];
-    rep->accused_instances = xc.counts[X::CNT_INSTANCES];
-    rep->view_overflows = xc.counts[X::CNT_VIEW_OVERFLOWS];
-    return BFTSIM_OK;
-}
-// ---- the chronicler (SPEC.md §11h): a third continuation of audit_device, run after the tally's synchronisation over
-// the records, statuses, signers and certificate rows, which it only reads. Its tables are one more piece of the pool.
-namespace {
-struct TimelineCont {
-    uint32_t tl_cap;
-    const bftsim_timeline_out* out;   // the caller's
-    bftsim_timeline_report* report;
-    uint64_t bytes, o_keys, o_nkeys, o_flags, o_open, o_pround, o_rcmax, o_rctop, o_pdig, o_pvot, o_pframe, o_pq, o_rcq,
-        o_rcmf, o_rcf, o_rflags, o_counts;
-    unsigned long long counts[bft::timeline::CNT_WORDS];
-    float ms[2];                      // walk, rows
-};
-}  // namespace
-static int timeline_layout(bftsim* h, TimelineCont& tc, uint64_t inst, uint32_t max_heights) {
-    namespace T = bft::timeline;
-    const uint64_t rows = inst * max_heights, Rx = rows ? rows : 1, Ix = inst ? inst : 1;
-    if (rows >= (1ull << 31) - 1) return fail(h, BFTSIM_ENOMEM, "bftsim_timeline: 2^31 rows or more");
-    if (tc.tl_cap == 0) tc.tl_cap = T::default_cap(max_heights);
-    if (tc.tl_cap > (1ull << 40) / sizeof(T::Key) / Ix)
-        return fail(h, BFTSIM_ENOMEM, "bftsim_timeline: tl_cap x instances above 1 TiB of key tables");
-    uint64_t bytes = 0;
-    auto sized = [&](uint64_t b) { const uint64_t o = bytes; bytes += (b + 31) & ~31ull; return o; };
-    tc.o_keys = sized(Ix * tc.tl_cap * sizeof(T::Key));
-    tc.o_nkeys = sized(Ix * 4); tc.o_flags = sized(Ix * 4); tc.o_open = sized(Ix * 4);
-    tc.o_pround = sized(Rx * 2); tc.o_rcmax = sized(Rx * 2); tc.o_rctop = sized(Rx * 2);             // preset to ROUND_NONE
-    tc.o_pdig = sized(Rx * 32); tc.o_pvot = sized(Rx * 32); tc.o_pframe = sized(Rx * 4); tc.o_pq = sized(Rx * 2);
-    tc.o_rcq = sized(Rx * 2); tc.o_rcmf = sized(Rx * 4); tc.o_rcf = sized(Rx * 4); tc.o_rflags = sized(Rx);
-    tc.o_counts = sized(T::CNT_WORDS * 8);
-    tc.bytes = bytes;
-    return BFTSIM_OK;
-}
-static int timeline_passes(bftsim* h, TimelineCont& tc, uint8_t* p, const bft::audit::Recs& r, const uint8_t* d_status,
-                           const int32_t* d_signer, const uint64_t* d_if0, uint64_t inst, uint32_t max_heights,
-                           const bft::timeline::Certs& certs, hipStream_t s) {
-    namespace T = bft::timeline;
-    const T::Rows rows{(uint16_t*)(p + tc.o_pround), p + tc.o_pdig, (uint64_t*)(p + tc.o_pvot), (uint32_t*)(p + tc.o_pframe),
-                       (uint16_t*)(p + tc.o_pq), (uint16_t*)(p + tc.o_rcq), (uint16_t*)(p + tc.o_rcmax),
-                       (uint32_t*)(p + tc.o_rcmf), (uint16_t*)(p + tc.o_rctop), (uint32_t*)(p + tc.o_rcf), p + tc.o_rflags};
-    const T::Args a{r, d_status, d_signer, d_if0, inst, h->cfg.n, tc.tl_cap, max_heights, bftsim_two_thirds_majority(h->cfg.n),
-                    certs, (T::Key*)(p + tc.o_keys), (uint32_t*)(p + tc.o_nkeys), (uint32_t*)(p + tc.o_flags),
-                    (uint32_t*)(p + tc.o_open), rows, (unsigned long long*)(p + tc.o_counts)};
-    Events ev;
-    HIPCHECK(h, ev.create(3));
-    HIPCHECK(h, hipMemsetAsync(p + tc.o_nkeys, 0, tc.o_pround - tc.o_nkeys, s));
-    HIPCHECK(h, hipMemsetAsync(p + tc.o_pround, 0xff, tc.o_pdig - tc.o_pround, s));    // ROUND_NONE
-    HIPCHECK(h, hipMemsetAsync(p + tc.o_pdig, 0, tc.bytes - tc.o_pdig, s));            // the other rows, the counters
-    HIPCHECK(h, hipEventRecord(ev[0], s));
-    HIPCHECK(h, T::launch_walk(a, s));
-    HIPCHECK(h, hipEventRecord(ev[1], s));
-    HIPCHECK(h, T::launch_rows(a, s));
-    HIPCHECK(h, hipEventRecord(ev[2], s));
-    HIPCHECK(h, hipMemcpyAsync(tc.counts, p + tc.o_counts, sizeof tc.counts, hipMemcpyDeviceToHost, s));
-    HIPCHECK(h, hipStreamSynchronize(s));
-    for (int k = 0; k < 2; ++k) HIPCHECK(h, hipEventElapsedTime(&tc.ms[k], ev[k], ev[k + 1]));
-    return BFTSIM_OK;
-}
-static int timeline_copy(bftsim* h, TimelineCont& tc, const uint8_t* p, uint64_t inst, uint32_t max_heights, hipStream_t s) {
-    namespace T = bft::timeline;
-    const uint64_t rows = inst * max_heights;
-    const bftsim_timeline_out* o = tc.out;
-    Events ev;
-    HIPCHECK(h, ev.create(2));
-    HIPCHECK(h, hipEventRecord(ev[0], s));
-    const struct { void* dst; uint64_t off, b; } back[] = {
-        {o->prep_round, tc.o_pround, rows * 2}, {o->prep_digest, tc.o_pdig, rows * 32}, {o->prep_voters, tc.o_pvot, rows * 32},
-        {o->prep_frame, tc.o_pframe, rows * 4}, {o->prep_quorums, tc.o_pq, rows * 2}, {o->rc_quorums, tc.o_rcq, rows * 2},
-        {o->rc_max_round, tc.o_rcmax, rows * 2}, {o->rc_max_frame, tc.o_rcmf, rows * 4}, {o->rc_top_round, tc.o_rctop, rows * 2},
-        {o->rc_frames, tc.o_rcf, rows * 4}, {o->flags, tc.o_rflags, rows}, {o->inst_flags, tc.o_flags, inst * 4},
-        {o->open_height, tc.o_open, inst * 4}};
-    for (const auto& k : back)
-        if (k.dst && k.b) HIPCHECK(h, hipMemcpyAsync(k.dst, p + k.off, k.b, hipMemcpyDeviceToHost, s));
-    HIPCHECK(h, hipEventRecord(ev[1], s));
-    HIPCHECK(h, hipStreamSynchronize(s));
-    float copy_ms = 0;
-    HIPCHECK(h, hipEventElapsedTime(&copy_ms, ev[0], ev[1]));
-    h->timeline_ms[0] = h->audit_ms[0] + h->audit_ms[1] + h->audit_ms[2];
-    h->timeline_ms[1] = tc.ms[0]; h->timeline_ms[2] = tc.ms[1]; h->timeline_ms[3] = h->audit_ms[3] + copy_ms;
-    bftsim_timeline_report* rep = tc.report;
-    memset(rep, 0, sizeof *rep);
-    rep->prepare_frames = tc.counts[T::CNT_PREPARE_FRAMES];
-    rep->rc_frames = tc.counts[T::CNT_RC_FRAMES];
-    rep->out_of_range = tc.counts[T::CNT_OUT_OF_RANGE];
-    rep->prepared = tc.counts[T::CNT_PREPARED];
-    rep->rc_quorums = tc.counts[T::CNT_RC_QUORUMS];
-    rep->rc_heights = tc.counts[T::CNT_RC_HEIGHTS];
-    rep->prepared_first = tc.counts[T::CNT_PREPARED_FIRST];
-    rep->cert_unprepared = tc.counts[T::CNT_CERT_UNPREPARED];
-    rep->locked_open = tc.counts[T::CNT_LOCKED_OPEN];
-    rep->key_overflows = tc.counts[T::CNT_KEY_OVERFLOWS];
-    return BFTSIM_OK;
-}
-// ---- the roll call (SPEC.md §11i): a fourth continuation of audit_device. It lays out and runs the chronicler's piece
-// (timeline_layout, timeline_passes) and then its own passes over the chronicler's key tables, which it only reads.
-namespace {
-struct RollCont {
-    TimelineCont tc;                  // out and report: the caller's, or stand-ins
-    const bftsim_rollcall_out* out;   // the caller's
-    bftsim_rollcall_report* report;
-    uint64_t rec_cap, bytes, o_tl, o_views, o_nviews, o_pos, o_frames, o_lh, o_lf, o_due, o_prop, o_miss, o_won, o_silent,
-        o_flags, o_recs, o_counts, o_scan;
-    size_t scan_bytes;
-    unsigned long long counts[bft::rollcall::CNT_WORDS];
-    uint32_t total;                   // the scan's
-    float ms[3];                      // views, walk, scan + gather
-};
-}  // namespace
-static int rollcall_layout(bftsim* h, RollCont& rc, uint64_t inst, uint32_t max_heights) {
-    namespace R = bft::rollcall;
-    if (int e = timeline_layout(h, rc.tc, inst, max_heights)) return e;
-    const uint64_t Ix = inst ? inst : 1, rows = inst * h->cfg.n, Rx = rows ? rows : 1;
-    const uint64_t vcap = R::view_cap(max_heights, rc.tc.tl_cap);
-    if (rows >= (1ull << 31) - 1) return fail(h, BFTSIM_ENOMEM, "bftsim_rollcall: 2^31 rows or more");
-    if (vcap > (1ull << 40) / sizeof(R::View) / Ix)
-        return fail(h, BFTSIM_ENOMEM, "bftsim_rollcall: views x instances above 1 TiB of view tables");
-    const uint64_t most = Ix * vcap;                                               // every view of the call
-    rc.rec_cap = rc.out->records ? (rc.out->rec_cap < most ? rc.out->rec_cap : most) : 0;
-    uint64_t bytes = rc.tc.bytes;
-    auto sized = [&](uint64_t b) { const uint64_t o = bytes; bytes += (b + 31) & ~31ull; return o; };
-    rc.o_tl = 0;
-    rc.o_views = sized(most * sizeof(R::View));
-    rc.o_nviews = sized((inst + 1) * 4); rc.o_pos = sized((inst + 1) * 4);
-    rc.o_frames = sized(Rx * 16); rc.o_lh = sized(Rx * 4); rc.o_lf = sized(Rx * 4); rc.o_due = sized(Rx * 4);
-    rc.o_prop = sized(Rx * 4); rc.o_miss = sized(Rx * 4); rc.o_won = sized(Rx * 4);
-    rc.o_silent = sized(Ix * 32); rc.o_flags = sized(Ix * 4);
-    rc.o_recs = sized((rc.rec_cap ? rc.rec_cap : 1) * sizeof(R::Record));
-    rc.o_counts = sized(R::CNT_WORDS * 8);
-    rc.scan_bytes = 0;
-    HIPCHECK(h, hipcub::DeviceScan::ExclusiveSum(nullptr, rc.scan_bytes, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)(inst + 1)));
-    rc.o_scan = sized(rc.scan_bytes ? rc.scan_bytes : 1);
-    rc.bytes = bytes;
-    return BFTSIM_OK;
-}
-static int rollcall_passes(bftsim* h, RollCont& rc, uint8_t* p, const bft::audit::Recs& r, const uint8_t* d_status,
-                           const int32_t* d_signer, const uint64_t* d_if0, uint64_t inst, uint32_t max_heights,
-                           const bft::timeline::Certs& certs, hipStream_t s) {
-    namespace R = bft::rollcall;
-    if (int e = timeline_passes(h, rc.tc, p + rc.o_tl, r, d_status, d_signer, d_if0, inst, max_heights, certs, s)) return e;
-    const R::Rows rows{(uint32_t*)(p + rc.o_frames), (uint32_t*)(p + rc.o_lh), (uint32_t*)(p + rc.o_lf), (uint32_t*)(p + rc.o_due),
-                       (uint32_t*)(p + rc.o_prop), (uint32_t*)(p + rc.o_miss), (uint32_t*)(p + rc.o_won)};
-    const R::Args a{r, d_status, d_signer, d_if0, inst, h->cfg.n, rc.tc.tl_cap, max_heights,
-                    h->cfg.seed_byte_order == BFTSIM_SEED_LE ? 1u : 0u, h->d_ghash, certs,
-                    (const bft::timeline::Key*)(p + rc.o_tl + rc.tc.o_keys), (const uint32_t*)(p + rc.o_tl + rc.tc.o_nkeys),
-                    (const uint32_t*)(p + rc.o_tl + rc.tc.o_flags), (R::View*)(p + rc.o_views), (uint32_t*)(p + rc.o_nviews),
-                    (uint32_t*)(p + rc.o_pos), rows, (uint64_t*)(p + rc.o_silent), (uint32_t*)(p + rc.o_flags),
-                    (R::Record*)(p + rc.o_recs), rc.rec_cap, (unsigned long long*)(p + rc.o_counts)};
-    Events ev;
-    HIPCHECK(h, ev.create(4));
-    HIPCHECK(h, hipMemsetAsync(p + rc.o_nviews, 0, rc.o_recs - rc.o_nviews, s));      // instances without a wave, the bitmaps' tails
-    HIPCHECK(h, hipMemsetAsync(p + rc.o_counts, 0, R::CNT_WORDS * 8, s));
-    HIPCHECK(h, hipEventRecord(ev[0], s));
-    HIPCHECK(h, R::launch_views(a, s));
-    HIPCHECK(h, hipEventRecord(ev[1], s));
-    HIPCHECK(h, R::launch_walk(a, s));
-    HIPCHECK(h, hipEventRecord(ev[2], s));
-    HIPCHECK(h, hipcub::DeviceScan::ExclusiveSum(p + rc.o_scan, rc.scan_bytes, a.inst_views, a.pos, (int)(inst + 1), s));
-    HIPCHECK(h, R::launch_gather(a, s));
-    HIPCHECK(h, hipEventRecord(ev[3], s));
-    HIPCHECK(h, hipMemcpyAsync(rc.counts, p + rc.o_counts, sizeof rc.counts, hipMemcpyDeviceToHost, s));
-    HIPCHECK(h, hipMemcpyAsync(&rc.total, a.pos + inst, 4, hipMemcpyDeviceToHost, s));
-    HIPCHECK(h, hipStreamSynchronize(s));
-    for (int k = 0; k < 3; ++k) HIPCHECK(h, hipEventElapsedTime(&rc.ms[k], ev[k], ev[k + 1]));
-    if (rc.total != rc.counts[R::CNT_VIEWS])
-        return fail(h, BFTSIM_EHIP, "bftsim_rollcall: the scan's total disagrees with the walk's count");
-    return BFTSIM_OK;
-}
-static int rollcall_copy(bftsim* h, RollCont& rc, const uint8_t* p, uint64_t inst, uint32_t max_heights, hipStream_t s) {
-    namespace R = bft::rollcall;
-    float kept[4];                                                 // bftsim_timeline_last_ms speaks of the last timeline call
-    memcpy(kept, h->timeline_ms, sizeof kept);
-    const int e = timeline_copy(h, rc.tc, p + rc.o_tl, inst, max_heights, s);
-    const float tl_ms = h->timeline_ms[1] + h->timeline_ms[2], tl_copy = h->timeline_ms[3];
-    memcpy(h->timeline_ms, kept, sizeof kept);
-    if (e) return e;
-    const uint64_t rows = inst * h->cfg.n, written = rc.total < rc.rec_cap ? rc.total : rc.rec_cap;
-    const bftsim_rollcall_out* o = rc.out;
-    Events ev;
-    HIPCHECK(h, ev.create(2));
-    HIPCHECK(h, hipEventRecord(ev[0], s));
-    const struct { void* dst; uint64_t off, b; } back[] = {
-        {o->frames, rc.o_frames, rows * 16}, {o->last_height, rc.o_lh, rows * 4}, {o->last_frame, rc.o_lf, rows * 4},
-        {o->due, rc.o_due, rows * 4}, {o->proposed, rc.o_prop, rows * 4}, {o->missed, rc.o_miss, rows * 4},
-        {o->won, rc.o_won, rows * 4}, {o->inst_views, rc.o_nviews, inst * 4}, {o->inst_silent, rc.o_silent, inst * 32},
-        {o->inst_flags, rc.o_flags, inst * 4}, {o->records, rc.o_recs, written * sizeof(R::Record)}};
-    for (const auto& k : back)
-        if (k.dst && k.b) HIPCHECK(h, hipMemcpyAsync(k.dst, p + k.off, k.b, hipMemcpyDeviceToHost, s));
-    HIPCHECK(h, hipEventRecord(ev[1], s));
-    HIPCHECK(h, hipStreamSynchronize(s));
-    float copy_ms = 0;
-    HIPCHECK(h, hipEventElapsedTime(&copy_ms, ev[0], ev[1]));
-    h->rollcall_ms[0] = h->audit_ms[0] + h->audit_ms[1] + h->audit_ms[2];
-    h->rollcall_ms[1] = tl_ms;
-    for (int k = 0; k < 3; ++k) h->rollcall_ms[2 + k] = rc.ms[k];
-    h->rollcall_ms[5] = tl_copy + copy_ms;
-    bftsim_rollcall_report* rep = rc.report;
-    memset(rep, 0, sizeof *rep);
-    rep->frames = rc.counts[R::CNT_FRAMES];
-    rep->out_of_range = rc.counts[R::CNT_OUT_OF_RANGE];
-    rep->views = rc.counts[R::CNT_VIEWS];
-    for (int k = 0; k < 3; ++k) rep->by_outcome[k] = rc.counts[R::CNT_OUTCOME + k];
-    rep->won = rc.counts[R::CNT_WON];
-    rep->silent = rc.counts[R::CNT_SILENT];
-    rep->silent_instances = rc.counts[R::CNT_SILENT_INST];
-    rep->partial_instances = rc.counts[R::CNT_PARTIAL_INST];
-    return BFTSIM_OK;
-}
-// the passes over a device stream: frame k = d_stream[d_foff[k] - base, d_foff[k + 1] - base),
-// if0 on the host. Every temporary is freed before returning; only the caller's buffers and h->audit_ms are written.
-static int audit_device(bftsim* h, const uint8_t* d_stream, const uint64_t* d_foff, uint64_t base, uint64_t frames,
-                        const uint64_t* if0, uint64_t inst, uint32_t max_heights, uint32_t key_cap,
-                        const bftsim_audit_out* out, bftsim_audit_report* report, hipStream_t s, float copy_in_ms,
-                        ArchiveCont* ac = nullptr, AccuseCont* xc = nullptr, TimelineCont* tc = nullptr,
-                        RollCont* rc = nullptr) {
-    namespace A = bft::audit;
-    SigApi& sa = sig_api();
-    if (key_cap == 0) key_cap = 4u * max_heights + 64u;
-    const uint64_t F = frames, Fx = F ? F : 1, Ix = inst ? inst : 1, rows = inst * max_heights, Rx = rows ? rows : 1;
-    if (key_cap > (1ull << 40) / sizeof(A::Key) / Ix)
-        return fail(h, BFTSIM_ENOMEM, "bftsim_audit: key_cap x instances above 1 TiB of key tables");
-    uint64_t bytes = 0;
-    auto sized = [&](uint64_t b) { const uint64_t o = bytes; bytes += (b + 31) & ~31ull; return o; };
-    const uint64_t o_st = sized(Fx), o_code = sized(Fx), o_hx = sized(Fx * 4), o_round = sized(Fx * 8), o_dig = sized(Fx * 32),
-                   o_sdig = sized(Fx * 32), o_sig = sized(Fx * 65), o_sk = sized(Fx * 4), o_want = sized(Fx * 4),
-                   o_sldig = sized(Fx * 32), o_seal = sized(Fx * 65), o_raddr = sized(Fx * 20), o_rok = sized(Fx),
-                   o_saddr = sized(Fx * 20), o_sok = sized(Fx), o_status = sized(Fx), o_signer = sized(Fx * 4),
-                   o_if0 = sized((inst + 1) * 8), o_keys = sized(Ix * key_cap * sizeof(A::Key)), o_iflags = sized(Ix * 4),
-                   o_cround = sized(Rx * 2), o_cdig = sized(Rx * 32), o_cvot = sized(Rx * 32), o_cframe = sized(Rx * 4),
-                   o_cflags = sized(Rx), o_counts = sized(A::CNT_WORDS * 8), o_nseal = sized(4);
-    const uint64_t o_arch = bytes;
-    if (ac) {                                                                      // the archiver's tables and slots
-        if (int rc = archive_layout(h, *ac, inst, max_heights)) return rc;
-        bytes += ac->bytes;
-    }
-    const uint64_t o_accuse = bytes;
-    if (xc) {                                                                      // the accuser's tables
-        if (int rc = accuse_layout(h, *xc, F, inst, max_heights)) return rc;
-        bytes += xc->bytes;
-    }
-    const uint64_t o_timeline = bytes;
-    if (tc) {                                                                      // the chronicler's tables and rows
-        if (int rc = timeline_layout(h, *tc, inst, max_heights)) return rc;
-        bytes += tc->bytes;
-    }
-    const uint64_t o_roll = bytes;
-    if (rc) {                                                                      // the chronicler's piece, then the roll call's
-        if (int e = rollcall_layout(h, *rc, inst, max_heights)) return e;
-        bytes += rc->bytes;
-    }
-    DevMem pool_mem;
-    if (pool_mem.alloc(bytes) != hipSuccess)
-        return fail(h, BFTSIM_ENOMEM, "bftsim_audit: " + std::to_string(bytes) + " bytes of device memory");
-    uint8_t* pool = pool_mem.as<uint8_t>();
-    A::Recs r{pool + o_st, pool + o_code, (uint32_t*)(pool + o_hx), (uint64_t*)(pool + o_round), pool + o_dig, pool + o_sdig,
-              pool + o_sig, (uint32_t*)(pool + o_sk), (uint32_t*)(pool + o_want), pool + o_sldig, pool + o_seal};
-    unsigned long long* d_counts = (unsigned long long*)(pool + o_counts);
-    uint32_t* d_nseal = (uint32_t*)(pool + o_nseal);
-    uint64_t* d_if0 = (uint64_t*)(pool + o_if0);
-    Events ev;
-    HIPCHECK(h, ev.create(5));
-    HIPCHECK(h, hipMemcpyAsync(d_if0, if0, (inst + 1) * 8, hipMemcpyHostToDevice, s));
-    HIPCHECK(h, hipMemsetAsync(d_counts, 0, A::CNT_WORDS * 8 + 4, s));            // the counters and n_seals
-    HIPCHECK(h, hipMemsetAsync(pool + o_cround, 0xff, Rx * 2, s));                // ROUND_NONE
-    HIPCHECK(h, hipMemsetAsync(pool + o_cdig, 0, o_counts - o_cdig, s));          // the other certificate rows
-    HIPCHECK(h, hipMemsetAsync(pool + o_iflags, 0, Ix * 4, s));
-    // decode
-    uint32_t n_seals = 0;
-    HIPCHECK(h, hipEventRecord(ev[0], s));
-    HIPCHECK(h, A::launch_decode(A::DecodeArgs{d_stream, d_foff, base, F, h->d_addr, h->cfg.n,
-                                               h->cfg.seed_byte_order == BFTSIM_SEED_LE ? 1u : 0u, max_heights, r, d_nseal}, s));
-    HIPCHECK(h, hipEventRecord(ev[1], s));
-    HIPCHECK(h, hipMemcpyAsync(&n_seals, d_nseal, 4, hipMemcpyDeviceToHost, s));
-    HIPCHECK(h, hipStreamSynchronize(s));
-    // recoveries: every frame's signer, every decodable Commit's seal
-    if (F && sa.recover(h->sig, r.sdig, r.sig, F, nullptr, pool + o_raddr, pool + o_rok, s) != 0)
-        return fail(h, BFTSIM_EHIP, std::string("bftsig_recover: ") + sa.last_error(h->sig));
-    if (n_seals && sa.recover(h->sig, r.seal_dig, r.seal, n_seals, nullptr, pool + o_saddr, pool + o_sok, s) != 0)
-        return fail(h, BFTSIM_EHIP, std::string("bftsig_recover (seals): ") + sa.last_error(h->sig));
-    HIPCHECK(h, hipEventRecord(ev[2], s));
-    // classification and tally
-    uint8_t* d_status = pool + o_status;
-    int32_t* d_signer = (int32_t*)(pool + o_signer);
-    HIPCHECK(h, A::launch_classify(A::ClassifyArgs{r, F, h->d_addr, h->cfg.n, pool + o_raddr, pool + o_rok, pool + o_saddr,
-                                                   pool + o_sok, d_status, d_signer, d_counts}, s));
-    HIPCHECK(h, A::launch_tally(A::TallyArgs{r, d_status, d_signer, d_if0, inst, (A::Key*)(pool + o_keys), key_cap, max_heights,
-                                             bftsim_two_thirds_majority(h->cfg.n), (uint32_t*)(pool + o_iflags),
-                                             (uint16_t*)(pool + o_cround), pool + o_cdig, (uint64_t*)(pool + o_cvot),
-                                             (uint32_t*)(pool + o_cframe), pool + o_cflags, d_counts}, s));
-    HIPCHECK(h, hipEventRecord(ev[3], s));
-    unsigned long long c[A::CNT_WORDS] = {0};
-    HIPCHECK(h, hipMemcpyAsync(c, d_counts, sizeof c, hipMemcpyDeviceToHost, s));
-    HIPCHECK(h, hipStreamSynchronize(s));      // every pass succeeded: only now the caller's buffers
-    if (ac) {
-        const bft::archive::Certs certs{(const uint16_t*)(pool + o_cround), pool + o_cdig, (const uint64_t*)(pool + o_cvot),
-                                        (const uint32_t*)(pool + o_cframe)};
-        if (int rc = archive_passes(h, *ac, pool + o_arch, d_stream, d_foff, base, F, r, d_status, d_signer, d_if0, inst,
-                                    max_heights, certs, s))
-            return rc;
-    }
-    if (xc)
-        if (int rc = accuse_passes(h, *xc, pool + o_accuse, F, r, d_status, d_signer, d_if0, inst, s)) return rc;
-    if (tc) {
-        const bft::timeline::Certs certs{(const uint16_t*)(pool + o_cround), pool + o_cdig, (const uint32_t*)(pool + o_cframe)};
-        if (int rc = timeline_passes(h, *tc, pool + o_timeline, r, d_status, d_signer, d_if0, inst, max_heights, certs, s)) return rc;
-    }
-    if (rc) {
-        const bft::timeline::Certs certs{(const uint16_t*)(pool + o_cround), pool + o_cdig, (const uint32_t*)(pool + o_cframe)};
-        if (int e = rollcall_passes(h, *rc, pool + o_roll, r, d_status, d_signer, d_if0, inst, max_heights, certs, s)) return e;
-    }
-    if (out) {
-        const struct { void* dst; uint64_t off, b; } back[] = {
-            {out->frame_status, o_status, F}, {out->frame_signer, o_signer, F * 4}, {out->inst_flags, o_iflags, inst * 4},
-            {out->cert_round, o_cround, rows * 2}, {out->cert_digest, o_cdig, rows * 32}, {out->cert_voters, o_cvot, rows * 32},
-            {out->cert_frame, o_cframe, rows * 4}, {out->cert_flags, o_cflags, rows}};
-        for (const auto& k : back)
-            if (k.dst && k.b) HIPCHECK(h, hipMemcpyAsync(k.dst, pool + k.off, k.b, hipMemcpyDeviceToHost, s));
-    }
-    HIPCHECK(h, hipEventRecord(ev[4], s));
-    HIPCHECK(h, hipStreamSynchronize(s));
-    float ms[4] = {0, 0, 0, 0};
-    for (int k = 0; k < 4; ++k) HIPCHECK(h, hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]));
-    h->audit_ms[0] = ms[0]; h->audit_ms[1] = ms[1]; h->audit_ms[2] = ms[2]; h->audit_ms[3] = ms[3] + copy_in_ms;
-    memset(report, 0, sizeof *report);
-    report->frames = F;
-    report->ok = c[A::CNT_STATUS + 0]; report->undecodable = c[A::CNT_STATUS + 1]; report->unrecoverable = c[A::CNT_STATUS + 2];
-    report->not_validator = c[A::CNT_STATUS + 3]; report->seal_bad = c[A::CNT_STATUS + 4];
-    report->seal_foreign = c[A::CNT_STATUS + 5];
-    for (int k = 0; k < 4; ++k) report->by_code[k] = c[A::CNT_CODE + k];
-    report->out_of_range = c[A::CNT_OUT_OF_RANGE];
-    report->certified = c[A::CNT_CERTIFIED];
-    report->conflicts = c[A::CNT_CONFLICTS];
-    report->key_overflows = c[A::CNT_KEY_OVERFLOWS];
-    report->recoveries = F + n_seals;
-    if (xc) return accuse_copy(h, *xc, pool + o_accuse, F, inst, s);
-    if (tc) return timeline_copy(h, *tc, pool + o_timeline, inst, max_heights, s);
-    if (rc) return rollcall_copy(h, *rc, pool + o_roll, inst, max_heights, s);
-    return ac ? archive_copy(h, *ac, pool + o_arch, inst, max_heights, s) : BFTSIM_OK;
-}
-static int audit_dims(bftsim* h, uint64_t frames, uint64_t inst, uint32_t max_heights, const char* what) {
-    if (max_heights == 0 || max_heights > 65535u) return fail(h, BFTSIM_EINVAL, std::string(what) + ": max_heights outside 1..65535");
-    if (frames >= (1ull << 32)) return fail(h, BFTSIM_EINVAL, std::string(what) + ": 2^32 frames or more");
-    if (inst >= (1ull << 31)) return fail(h, BFTSIM_EINVAL, std::string(what) + ": 2^31 instances or more");
-    return BFTSIM_OK;
-}
-
-// the observer over a host stream; ac: the archiver's continuation (null for bftsim_audit_trace)
-static int audit_host_stream(bftsim* h, const uint8_t* stream, uint64_t stream_bytes, const uint64_t* frame_off, uint64_t frames,
-                             const uint64_t* inst_frame0, uint64_t inst_count, uint32_t max_heights, uint32_t key_cap,
-                             const bftsim_audit_out* out, bftsim_audit_report* report, ArchiveCont* ac,
-                             AccuseCont* xc = nullptr, TimelineCont* tc = nullptr, RollCont* rc = nullptr) {
-    if (!frame_off || !inst_frame0 || (stream_bytes && !stream))
-        return fail(h, BFTSIM_EINVAL, "bftsim_audit_trace: null stream, frame_off or inst_frame0");
-    if (int rc = audit_dims(h, frames, inst_count, max_heights, "bftsim_audit_trace")) return rc;
-    for (uint64_t k = 0; k < frames; ++k)
-        if (frame_off[k] > frame_off[k + 1]) return fail(h, BFTSIM_EINVAL, "bftsim_audit_trace: frame_off decreases");
-    if (frame_off[frames] != stream_bytes) return fail(h, BFTSIM_EINVAL, "bftsim_audit_trace: frame_off does not end at stream_bytes");
-    for (uint64_t i = 0; i < inst_count; ++i)
-        if (inst_frame0[i] > inst_frame0[i + 1]) return fail(h, BFTSIM_EINVAL, "bftsim_audit_trace: inst_frame0 decreases");
-    if (inst_frame0[0] != 0 || inst_frame0[inst_count] != frames)
-        return fail(h, BFTSIM_EINVAL, "bftsim_audit_trace: inst_frame0 does not run from 0 to frames");
-    HIPCHECK(h, hipSetDevice(h->device));
-    if (int rc = audit_sig(h)) return rc;
-    hipStream_t s = h->last_stream;
-    DevMem in_mem;
-    const uint64_t sb = (stream_bytes + 15) & ~15ull;              // the frame offsets follow the padded stream
-    if (in_mem.alloc(sb + 16 + (frames + 1) * 8) != hipSuccess)
-        return fail(h, BFTSIM_ENOMEM, "bftsim_audit_trace: device memory for the stream");
-    uint8_t* d_in = in_mem.as<uint8_t>();
-    Events ev;
-    float copy_ms = 0;
-    HIPCHECK(h, ev.create(2));
-    HIPCHECK(h, hipEventRecord(ev[0], s));
-    if (stream_bytes) HIPCHECK(h, hipMemcpyAsync(d_in, stream, stream_bytes, hipMemcpyHostToDevice, s));
-    HIPCHECK(h, hipMemcpyAsync(d_in + sb + 16, frame_off, (frames + 1) * 8, hipMemcpyHostToDevice, s));
-    HIPCHECK(h, hipEventRecord(ev[1], s));
-    HIPCHECK(h, hipStreamSynchronize(s));
-    HIPCHECK(h, hipEventElapsedTime(&copy_ms, ev[0], ev[1]));
-    return audit_device(h, d_in, (const uint64_t*)(d_in + sb + 16), 0, frames, inst_frame0, inst_count, max_heights, key_cap,
-                        out, report, s, copy_ms, ac, xc, tc, rc);
-}
-int bftsim_audit_trace(bftsim_t* h, const uint8_t* stream, uint64_t stream_bytes, const uint64_t* frame_off, uint64_t frames,
-                       const uint64_t* inst_frame0, uint64_t inst_count, uint32_t max_heights, uint32_t key_cap,
-                       const bftsim_audit_out* out, bftsim_audit_report* report) {
-    if (!h || !report) return BFTSIM_EINVAL;
-    return audit_host_stream(h, stream, stream_bytes, frame_off, frames, inst_frame0, inst_count, max_heights, key_cap, out,
-                             report, nullptr);
-}
-
-// the observer over the kept trace of the last launch; ac as above
-static int audit_kept_trace(bftsim* h, uint64_t inst_begin, uint64_t inst_count, uint32_t key_cap,
-                            const bftsim_audit_out* out, bftsim_audit_report* report, ArchiveCont* ac,
-                            AccuseCont* xc = nullptr, TimelineCont* tc = nullptr, RollCont* rc = nullptr) {
-    if (int rc = trace_ready(h, "bftsim_audit_last_trace")) return rc;
-    const uint64_t n = h->trace_n;
-    if (inst_begin > n || inst_count > n - inst_begin)
-        return fail(h, BFTSIM_EINVAL, "bftsim_audit_last_trace: instances [" + std::to_string(inst_begin) + ", +" +
-                                          std::to_string(inst_count) + ") outside the last launch of " + std::to_string(n));
-    if (int rc = trace_size_pass(h)) return rc;
-    const uint64_t m0 = h->trace_moff[inst_begin], m1 = h->trace_moff[inst_begin + inst_count];
-    const uint64_t frames = m1 - m0, base = h->trace_ioff[inst_begin], bytes = h->trace_ioff[inst_begin + inst_count] - base;
-    if (int rc = audit_dims(h, frames, inst_count, h->cfg.heights, "bftsim_audit_last_trace")) return rc;
-    HIPCHECK(h, hipSetDevice(h->device));
-    if (int rc = audit_sig(h)) return rc;
-    hipStream_t s = h->last_stream;
-    std::vector<uint64_t> if0(inst_count + 1);
-    for (uint64_t i = 0; i <= inst_count; ++i) if0[i] = h->trace_moff[inst_begin + i] - m0;
-    // the emit pass of bftsim_export_trace into a device stream that stays on the device
-    DevMem d_out;
-    if (d_out.alloc(((bytes + 15) & ~15ull) + 16) != hipSuccess)
-        return fail(h, BFTSIM_ENOMEM, "bftsim_audit_last_trace: device memory for the stream");
-    if (int rc = trace_emit(h, "bftsim_audit_last_trace", m0, m1, d_out.as<uint8_t>(), nullptr, nullptr)) return rc;
-    return audit_device(h, d_out.as<uint8_t>(), h->d_tfoff + m0, base, frames, if0.data(), inst_count, h->cfg.heights,
-                        key_cap, out, report, s, 0.f, ac, xc, tc, rc);
-}
-int bftsim_audit_last_trace(bftsim_t* h, uint64_t inst_begin, uint64_t inst_count, uint32_t key_cap,
-                            const bftsim_audit_out* out, bftsim_audit_report* report) {
-    if (!h || !report) return BFTSIM_EINVAL;
-    return audit_kept_trace(h, inst_begin, inst_count, key_cap, out, report, nullptr);
-}
-
-int bftsim_audit_last_ms(bftsim_t* h, float* decode_ms, float* recover_ms, float* tally_ms, float* copy_ms) {
-    if (!h) return BFTSIM_EINVAL;
-    if (decode_ms) *decode_ms = h->audit_ms[0];
-    if (recover_ms) *recover_ms = h->audit_ms[1];
-    if (tally_ms) *tally_ms = h->audit_ms[2];
-    if (copy_ms) *copy_ms = h->audit_ms[3];
-    return BFTSIM_OK;
-}
-
-// ---- the archiver's entry points (SPEC.md §11e): the observer's passes and refusals, then pick, emit and heights
-static int archive_args(bftsim* h, uint8_t* hdr, uint64_t slot_bytes, uint32_t* hdr_len, const char* what) {
-    if (!hdr || !hdr_len) return fail(h, BFTSIM_EINVAL, std::string(what) + ": null hdr or hdr_len");
-    if (slot_bytes < bftsim_ledger_slot_bytes(h->cfg.n)) return fail(h, BFTSIM_EINVAL, std::string(what) + ": slot_bytes too small");
-    return BFTSIM_OK;
-}
-int bftsim_archive_trace(bftsim_t* h, const uint8_t* stream, uint64_t stream_bytes, const uint64_t* frame_off, uint64_t frames,
-                         const uint64_t* inst_frame0, uint64_t inst_count, uint32_t max_heights, uint32_t key_cap,
-                         uint8_t* hdr, uint64_t slot_bytes, uint32_t* hdr_len, const bftsim_archive_out* out,
-                         const bftsim_audit_out* audit_out, bftsim_audit_report* audit_report, bftsim_archive_report* report) {
-    if (!h || !report) return BFTSIM_EINVAL;
-    if (int rc = archive_args(h, hdr, slot_bytes, hdr_len, "bftsim_archive_trace")) return rc;
-    ArchiveCont ac{};
-    ac.hdr = hdr; ac.slot_bytes = slot_bytes; ac.hdr_len = hdr_len; ac.out = out; ac.report = report;
-    bftsim_audit_report own;
-    return audit_host_stream(h, stream, stream_bytes, frame_off, frames, inst_frame0, inst_count, max_heights, key_cap,
-                             audit_out, audit_report ? audit_report : &own, &ac);
-}
-int bftsim_archive_last_trace(bftsim_t* h, uint64_t inst_begin, uint64_t inst_count, uint32_t key_cap, uint8_t* hdr,
-                              uint64_t slot_bytes, uint32_t* hdr_len, const bftsim_archive_out* out,
-                              const bftsim_audit_out* audit_out, bftsim_audit_report* audit_report,
-                              bftsim_archive_report* report) {
-    if (!h || !report) return BFTSIM_EINVAL;
-    if (int rc = archive_args(h, hdr, slot_bytes, hdr_len, "bftsim_archive_last_trace")) return rc;
-    ArchiveCont ac{};
-    ac.hdr = hdr; ac.slot_bytes = slot_bytes; ac.hdr_len = hdr_len; ac.out = out; ac.report = report;
-    bftsim_audit_report own;
-    return audit_kept_trace(h, inst_begin, inst_count, key_cap, audit_out, audit_report ? audit_report : &own, &ac);
-}
-int bftsim_archive_last_ms(bftsim_t* h, float* audit_ms, float* pick_ms, float* emit_ms, float* copy_ms) {
-    if (!h) return BFTSIM_EINVAL;
-    if (audit_ms) *audit_ms = h->archive_ms[0];
-    if (pick_ms) *pick_ms = h->archive_ms[1];
-    if (emit_ms) *emit_ms = h->archive_ms[2];
-    if (copy_ms) *copy_ms = h->archive_ms[3];
-    return BFTSIM_OK;
-}
-
-// ---- the accuser's entry points (SPEC.md §11g): the observer's passes and refusals, then walk, mark, scan and gather
-static int accuse_args(bftsim* h, const bftsim_accuse_out* out, const char* what) {
-    if (!out) return fail(h, BFTSIM_EINVAL, std::string(what) + ": null out");
-    if (out->rec_cap && !out->records) return fail(h, BFTSIM_EINVAL, std::string(what) + ": rec_cap without records");
-    return BFTSIM_OK;
-}
-int bftsim_accuse_trace(bftsim_t* h, const uint8_t* stream, uint64_t stream_bytes, const uint64_t* frame_off, uint64_t frames,
-                        const uint64_t* inst_frame0, uint64_t inst_count, uint32_t max_heights, uint32_t key_cap,
-                        uint32_t view_cap, const bftsim_accuse_out* out, const bftsim_audit_out* audit_out,
-                        bftsim_audit_report* audit_report, bftsim_accuse_report* report) {
-    if (!h || !report) return BFTSIM_EINVAL;
-    if (int rc = accuse_args(h, out, "bftsim_accuse_trace")) return rc;
-    AccuseCont xc{};
-    xc.view_cap = view_cap; xc.out = out; xc.report = report;
-    bftsim_audit_report own;
-    return audit_host_stream(h, stream, stream_bytes, frame_off, frames, inst_frame0, inst_count, max_heights, key_cap,
-                             audit_out, audit_report ? audit_report : &own, nullptr, &xc);
-}
-int bftsim_accuse_last_trace(bftsim_t* h, uint64_t inst_begin, uint64_t inst_count, uint32_t key_cap, uint32_t view_cap,
-                             const bftsim_accuse_out* out, const bftsim_audit_out* audit_out,
-                             bftsim_audit_report* audit_report, bftsim_accuse_report* report) {
-    if (!h || !report) return BFTSIM_EINVAL;
-    if (int rc = accuse_args(h, out, "bftsim_accuse_last_trace")) return rc;
-    AccuseCont xc{};
-    xc.view_cap = view_cap; xc.out = out; xc.report = report;
-    bftsim_audit_report own;
-    return audit_kept_trace(h, inst_begin, inst_count, key_cap, audit_out, audit_report ? audit_report : &own, nullptr, &xc);
-}
-int bftsim_accuse_last_ms(bftsim_t* h, float* audit_ms, float* walk_ms, float* compact_ms, float* copy_ms) {
-    if (!h) return BFTSIM_EINVAL;
-    if (audit_ms) *audit_ms = h->accuse_ms[0];
-    if (walk_ms) *walk_ms = h->accuse_ms[1];
-    if (compact_ms) *compact_ms = h->accuse_ms[2];
-    if (copy_ms) *copy_ms = h->accuse_ms[3];
-    return BFTSIM_OK;
-}
-
-// ---- the chronicler's entry points (SPEC.md §11h): the observer's passes and refusals, then walk and rows
-int bftsim_timeline_trace(bftsim_t* h, const uint8_t* stream, uint64_t stream_bytes, const uint64_t* frame_off, uint64_t frames,
-                          const uint64_t* inst_frame0, uint64_t inst_count, uint32_t max_heights, uint32_t key_cap,
-                          uint32_t tl_cap, const bftsim_timeline_out* out, const bftsim_audit_out* audit_out,
-                          bftsim_audit_report* audit_report, bftsim_timeline_report* report) {
-    if (!h || !report) return BFTSIM_EINVAL;
-    if (!out) return fail(h, BFTSIM_EINVAL, "bftsim_timeline_trace: null out");
-    TimelineCont tc{};
-    tc.tl_cap = tl_cap; tc.out = out; tc.report = report;
-    bftsim_audit_report own;
-    return audit_host_stream(h, stream, stream_bytes, frame_off, frames, inst_frame0, inst_count, max_heights, key_cap,
-                             audit_out, audit_report ? audit_report : &own, nullptr, nullptr, &tc);
-}
-int bftsim_timeline_last_trace(bftsim_t* h, uint64_t inst_begin, uint64_t inst_count, uint32_t key_cap, uint32_t tl_cap,
-                               const bftsim_timeline_out* out, const bftsim_audit_out* audit_out,
-                               bftsim_audit_report* audit_report, bftsim_timeline_report* report) {
-    if (!h || !report) return BFTSIM_EINVAL;
-    if (!out) return fail(h, BFTSIM_EINVAL, "bftsim_timeline_last_trace: null out");
-    TimelineCont tc{};
-    tc.tl_cap = tl_cap; tc.out = out; tc.report = report;
-    bftsim_audit_report own;
-    return audit_kept_trace(h, inst_begin, inst_count, key_cap, audit_out, audit_report ? audit_report : &own, nullptr, nullptr, &tc);
-}
-int bftsim_timeline_last_ms(bftsim_t* h, float* audit_ms, float* walk_ms, float* rows_ms, float* copy_ms) {
-    if (!h) return BFTSIM_EINVAL;
-    if (audit_ms) *audit_ms = h->timeline_ms[0];
-    if (walk_ms) *walk_ms = h->timeline_ms[1];
-    if (rows_ms) *rows_ms = h->timeline_ms[2];
-    if (copy_ms) *copy_ms = h->timeline_ms[3];
-    return BFTSIM_OK;
-}
-
-// ---- the roll call's entry points (SPEC.md §11i): the observer's passes and refusals, the chronicler's walk and rows,
-// then views, walk and gather
-namespace {
-struct RollStandIns {                 // what the chronicler's piece writes when the caller takes none of it
-    bftsim_timeline_out out;
-    bftsim_timeline_report report;
-};
-}  // namespace
-static int rollcall_args(bftsim* h, RollCont& rc, RollStandIns& own, uint32_t tl_cap, const bftsim_rollcall_out* out,
-                         bftsim_rollcall_report* report, const bftsim_timeline_out* timeline_out,
-                         bftsim_timeline_report* timeline_report, const char* what) {
-    if (!out) return fail(h, BFTSIM_EINVAL, std::string(what) + ": null out");
-    if (out->rec_cap && !out->records) return fail(h, BFTSIM_EINVAL, std::string(what) + ": rec_cap without records");
-    if (h->cfg.n > 256u) return fail(h, BFTSIM_EINVAL, std::string(what) + ": more than 256 validators");
-    memset(&own, 0, sizeof own);
-    rc.tc.tl_cap = tl_cap; rc.tc.out = timeline_out ? timeline_out : &own.out;
-    rc.tc.report = timeline_report ? timeline_report : &own.report;
-    rc.out = out; rc.report = report;
-    return BFTSIM_OK;
-}
-int bftsim_rollcall_trace(bftsim_t* h, const uint8_t* stream, uint64_t stream_bytes, const uint64_t* frame_off, uint64_t frames,
-                          const uint64_t* inst_frame0, uint64_t inst_count, uint32_t max_heights, uint32_t key_cap,
-                          uint32_t tl_cap, const bftsim_rollcall_out* out, bftsim_rollcall_report* report,
-                          const bftsim_audit_out* audit_out, bftsim_audit_report* audit_report,
-                          const bftsim_timeline_out* timeline_out, bftsim_timeline_report* timeline_report) {
-    if (!h || !report) return BFTSIM_EINVAL;
-    RollCont rc{};
-    RollStandIns own_tl;
-    if (int e = rollcall_args(h, rc, own_tl, tl_cap, out, report, timeline_out, timeline_report, "bftsim_rollcall_trace")) return e;
-    bftsim_audit_report own;
-    return audit_host_stream(h, stream, stream_bytes, frame_off, frames, inst_frame0, inst_count, max_heights, key_cap,
-                             audit_out, audit_report ? audit_report : &own, nullptr, nullptr, nullptr, &rc);
-}
-int bftsim_rollcall_last_trace(bftsim_t* h, uint64_t inst_begin, uint64_t inst_count, uint32_t key_cap, uint32_t tl_cap,
-                               const bftsim_rollcall_out* out, bftsim_rollcall_report* report,
-                               const bftsim_audit_out* audit_out, bftsim_audit_report* audit_report,
-                               const bftsim_timeline_out* timeline_out, bftsim_timeline_report* timeline_report) {
-    if (!h || !report) return BFTSIM_EINVAL;
-    RollCont rc{};
-    RollStandIns own_tl;
-    if (int e = rollcall_args(h, rc, own_tl, tl_cap, out, report, timeline_out, timeline_report, "bftsim_rollcall_last_trace")) return e;
-    bftsim_audit_report own;
-    return audit_kept_trace(h, inst_begin, inst_count, key_cap, audit_out, audit_report ? audit_report : &own, nullptr, nullptr,
-                            nullptr, &rc);
-}
-int bftsim_rollcall_last_ms(bftsim_t* h, float* audit_ms, float* timeline_ms, float* views_ms, float* walk_ms, float* gather_ms,
-                            float* copy_ms) {
-    if (!h) return BFTSIM_EINVAL;
-    float* const dst[6] = {audit_ms, timeline_ms, views_ms, walk_ms, gather_ms, copy_ms};
-    for (int k = 0; k < 6; ++k)
-        if (dst[k]) *dst[k] = h->rollcall_ms[k];
-    return BFTSIM_OK;
-}
-
-// ---- the importer (SPEC.md §11d): every header of a ledger verified from its bytes on the device
-// votes per header (average over the slots) from which the tally takes a wave per header instead of a lane. Measured
-// at 3 votes a header (the lane mapping 2.8x faster) and at 43 (the wave mapping 8.6x faster); the
-// crossover between them was not bisected, 16 is a quarter of a wave
-static constexpr uint32_t LEDGER_WAVE_MIN_VOTES = 16;
-int bftsim_set_ledger_votes(bftsim_t* h, uint32_t kind) {
-    if (!h) return BFTSIM_EINVAL;
-    if (kind != BFTSIM_VOTES_SIGNATURES && kind != BFTSIM_VOTES_SEALS)
-        return fail(h, BFTSIM_EINVAL, "bftsim_set_ledger_votes: kind is neither BFTSIM_VOTES_SIGNATURES nor BFTSIM_VOTES_SEALS");
-    h->ledger_votes = kind;
-    return BFTSIM_OK;
-}
-
-int bftsim_verify_ledger(bftsim_t* h, const uint8_t* hdr, uint64_t slot_bytes, const uint32_t* hdr_len, uint64_t inst_count,
-                         uint32_t max_heights, const bftsim_ledger_out* out, bftsim_ledger_report* report) {
-    namespace L = bft::ledger;
-    if (!h || !report) return BFTSIM_EINVAL;
-    if (!hdr || !hdr_len) return fail(h, BFTSIM_EINVAL, "bftsim_verify_ledger: null hdr or hdr_len");
-    if (max_heights == 0 || max_heights > 65535u) return fail(h, BFTSIM_EINVAL, "bftsim_verify_ledger: max_heights outside 1..65535");
-    if (slot_bytes == 0) return fail(h, BFTSIM_EINVAL, "bftsim_verify_ledger: slot_bytes is 0");
-    if (inst_count >= (1ull << 31)) return fail(h, BFTSIM_EINVAL, "bftsim_verify_ledger: 2^31 instances or more");
-    const uint64_t slots = inst_count * max_heights, Sx = slots ? slots : 1, Ix = inst_count ? inst_count : 1;
-    // the scan's item count is an int, and a vote's header index a uint32_t
-    if (slots >= (1ull << 31) - 1) return fail(h, BFTSIM_ENOMEM, "bftsim_verify_ledger: 2^31 header slots or more");
-    if (slot_bytes > (1ull << 40) / Sx) return fail(h, BFTSIM_ENOMEM, "bftsim_verify_ledger: above 1 TiB of header slots");
-    HIPCHECK(h, hipSetDevice(h->device));
-    if (int rc = audit_sig(h)) return rc;
-    SigApi& sa = sig_api();
-    hipStream_t s = h->last_stream;
-    // the A/B switch of scripts/ledger_bench.py, read only under BFTSIM_TESTING=1: 1 lane per header, 2 wave per header
-    uint32_t mapping = 0;
-    if (const char* t = getenv("BFTSIM_TESTING"); t && strcmp(t, "1") == 0)
-        if (const char* e = getenv("BFTSIM_LEDGER_TALLY")) mapping = (uint32_t)atoi(e);
-    uint64_t bytes = 0;
-    auto sized = [&](uint64_t b) { const uint64_t o = bytes; bytes += (b + 31) & ~31ull; return o; };
-    const uint64_t o_hdr = sized(Sx * slot_bytes), o_len = sized(Sx * 4), o_recs = sized(Sx * sizeof(L::Rec)),
-                   o_vbase = sized((Sx + 1) * 8), o_voters = sized(Sx * 32), o_dup = sized(Sx * 4), o_bad = sized(Sx),
-                   o_status = sized(Sx), o_bhash = sized(Sx * 32), o_nv = sized(Sx * 2), o_vh = sized(Ix * 8),
-                   o_counts = sized(L::CNT_WORDS * 8);
-    size_t tb = 0;
-    HIPCHECK(h, hipcub::DeviceScan::ExclusiveSum(nullptr, tb, (unsigned long long*)nullptr, (unsigned long long*)nullptr,
-                                                 (int)(slots + 1)));
-    const uint64_t o_scan = sized(tb ? tb : 1);
-    DevMem pool_mem;
-    if (pool_mem.alloc(bytes) != hipSuccess)
-        return fail(h, BFTSIM_ENOMEM, "bftsim_verify_ledger: " + std::to_string(bytes) + " bytes of device memory");
-    uint8_t* pool = pool_mem.as<uint8_t>();
-    L::Args a{};
-    a.hdr = pool + o_hdr; a.hdr_len = (const uint32_t*)(pool + o_len); a.slot_bytes = slot_bytes; a.slots = slots;
-    a.inst = (uint32_t)inst_count; a.H = max_heights; a.addresses = h->d_addr; a.n = h->cfg.n;
-    a.quorum = bftsim_two_thirds_majority(h->cfg.n); a.block_period = h->cfg.block_period; a.genesis_hash = h->d_ghash;
-    a.genesis_time = h->cfg.genesis_time; a.recs = (L::Rec*)(pool + o_recs); a.vbase = (unsigned long long*)(pool + o_vbase);
-    a.voters = (uint64_t*)(pool + o_voters); a.dup = (uint32_t*)(pool + o_dup); a.bad = pool + o_bad;
-    a.status = pool + o_status; a.bhash = pool + o_bhash; a.n_votes = (uint16_t*)(pool + o_nv);
-    a.vheight = (uint64_t*)(pool + o_vh); a.counts = (unsigned long long*)(pool + o_counts);
-    Events ev, evc;
-    HIPCHECK(h, ev.create(5));
-    HIPCHECK(h, evc.create(4));
-    HIPCHECK(h, hipEventRecord(evc[0], s));
-    if (slots) {
-        HIPCHECK(h, hipMemcpyAsync(pool + o_hdr, hdr, slots * slot_bytes, hipMemcpyHostToDevice, s));
-        HIPCHECK(h, hipMemcpyAsync(pool + o_len, hdr_len, slots * 4, hipMemcpyHostToDevice, s));
-    }
-    HIPCHECK(h, hipEventRecord(evc[1], s));
-    HIPCHECK(h, hipMemsetAsync(a.counts, 0, L::CNT_WORDS * 8, s));
-    HIPCHECK(h, hipMemsetAsync(a.vbase, 0, (Sx + 1) * 8, s));
-    HIPCHECK(h, hipMemsetAsync(a.vheight, 0, Ix * 8, s));
-    // decode, then the dense vote list: a scan of the headers' vote counts, a scatter
-    unsigned long long V = 0;
-    HIPCHECK(h, hipEventRecord(ev[0], s));
-    HIPCHECK(h, L::launch_decode(a, s));
-    HIPCHECK(h, hipcub::DeviceScan::ExclusiveSum(pool + o_scan, tb, a.vbase, a.vbase, (int)(slots + 1), s));
-    HIPCHECK(h, hipEventRecord(evc[2], s));    // the host's wait for the total and its allocation are not decode time
-    HIPCHECK(h, hipMemcpyAsync(&V, a.vbase + slots, 8, hipMemcpyDeviceToHost, s));
-    HIPCHECK(h, hipStreamSynchronize(s));
-    if (V > slots * (uint64_t)L::MAX_VOTES) return fail(h, BFTSIM_EHIP, "bftsim_verify_ledger: the vote scan disagrees with the decode pass");
-    const uint64_t Vx = V ? V : 1;
-    uint64_t vbytes = 0;
-    auto vsized = [&](uint64_t b) { const uint64_t o = vbytes; vbytes += (b + 31) & ~31ull; return o; };
-    const uint64_t v_sig = vsized(Vx * 65), v_dig = vsized(Vx * 32), v_addr = vsized(Vx * 20), v_ok = vsized(Vx),
-                   v_hdr = vsized(Vx * 4);
-    DevMem vote_mem;
-    if (vote_mem.alloc(vbytes) != hipSuccess)
-        return fail(h, BFTSIM_ENOMEM, "bftsim_verify_ledger: " + std::to_string(vbytes) + " bytes of device memory for the votes");
-    uint8_t* vp = vote_mem.as<uint8_t>();
-    a.votes = V; a.vsig = vp + v_sig; a.vdig = vp + v_dig; a.vaddr = vp + v_addr; a.vok = vp + v_ok;
-    a.vhdr = (uint32_t*)(vp + v_hdr);
-    HIPCHECK(h, hipEventRecord(evc[3], s));
-    HIPCHECK(h, L::launch_scatter(a, s));
-    HIPCHECK(h, hipEventRecord(ev[1], s));
-    // recoveries: every vote over its header's seal digest
-    if (V && sa.recover(h->sig, a.vdig, a.vsig, V, nullptr, a.vaddr, a.vok, s) != 0)
-        return fail(h, BFTSIM_EHIP, std::string("bftsig_recover: ") + sa.last_error(h->sig));
-    HIPCHECK(h, hipEventRecord(ev[2], s));
-    // a lane per header below this many votes per header on average, a wave per header from there
-    if (mapping != L::TALLY_LANE && mapping != L::TALLY_WAVE)
-        mapping = V < slots * (uint64_t)LEDGER_WAVE_MIN_VOTES ? L::TALLY_LANE : L::TALLY_WAVE;
-    HIPCHECK(h, L::launch_tally(a, mapping, s));
-    HIPCHECK(h, L::launch_link(a, s));
-    HIPCHECK(h, hipEventRecord(ev[3], s));
-    unsigned long long c[L::CNT_WORDS] = {0};
-    HIPCHECK(h, hipMemcpyAsync(c, a.counts, sizeof c, hipMemcpyDeviceToHost, s));
-    HIPCHECK(h, hipStreamSynchronize(s));      // every pass succeeded: only now the caller's buffers
-    if (out) {
-        const struct { void* dst; uint64_t off, b; } back[] = {
-            {out->status, o_status, slots}, {out->block_hash, o_bhash, slots * 32}, {out->voters, o_voters, slots * 32},
-            {out->n_votes, o_nv, slots * 2}, {out->verified_height, o_vh, inst_count * 8}};
-        for (const auto& k : back)
-            if (k.dst && k.b) HIPCHECK(h, hipMemcpyAsync(k.dst, pool + k.off, k.b, hipMemcpyDeviceToHost, s));
-    }
-    HIPCHECK(h, hipEventRecord(ev[4], s));
-    HIPCHECK(h, hipStreamSynchronize(s));
-    float ms[4] = {0, 0, 0, 0}, in_ms = 0;
-    for (int k = 0; k < 4; ++k) HIPCHECK(h, hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]));
-    HIPCHECK(h, hipEventElapsedTime(&in_ms, evc[0], evc[1]));
-    float scan_ms = 0, scatter_ms = 0;
-    HIPCHECK(h, hipEventElapsedTime(&scan_ms, ev[0], evc[2]));
-    HIPCHECK(h, hipEventElapsedTime(&scatter_ms, evc[3], ev[1]));
-    ms[0] = scan_ms + scatter_ms;              // decode kernel + scan, then the scatter: device time on either side of the wait
-    h->ledger_ms[0] = ms[0]; h->ledger_ms[1] = ms[1]; h->ledger_ms[2] = ms[2]; h->ledger_ms[3] = ms[3] + in_ms;
-    memset(report, 0, sizeof *report);
-    report->headers = c[L::CNT_HEADERS];
-    for (uint32_t k = 0; k < L::ST_COUNT; ++k) report->by_status[k] = c[L::CNT_STATUS + k];
-    report->votes = V;
-    report->recoveries = V;
-    report->duplicate_votes = c[L::CNT_DUP];
-    report->verified_instances = c[L::CNT_WHOLE];
-    return BFTSIM_OK;
-}
-
-int bftsim_ledger_last_ms(bftsim_t* h, float* decode_ms, float* recover_ms, float* tally_ms, float* copy_ms) {
-    if (!h) return BFTSIM_EINVAL;
-    if (decode_ms) *decode_ms = h->ledger_ms[0];
-    if (recover_ms) *recover_ms = h->ledger_ms[1];
-    if (tally_ms) *tally_ms = h->ledger_ms[2];
-    if (copy_ms) *copy_ms = h->ledger_ms[3];
-    return BFTSIM_OK;
+    return h ? last_ms(h->twin_ms, {index_ms, digest_ms, sign_ms}) : BFTSIM_EINVAL;
 }
 
 int bftsim_stats_get(bftsim_t* h, bftsim_stats* out) {

@@ -92,6 +92,39 @@ def test_stream_equals_reference(name, tl_cap):
         RC.check_against_run(got, c["cfg"], c["ref"]["res"], c["ref"]["first"])
 
 
+def test_family_shares_the_observer_and_each_call_keeps_its_own_ms():
+    """audit, archive, accuse, timeline and roll call in that order on one Simulator over "cfg1" (the fewest frames of
+    STREAMS: 71, one instance, 6 heights): every continuation's audit outputs are the plain audit's and the roll call's
+    timeline is timeline_trace's. The roll call runs the chronicler's passes but is no timeline call: timeline_ms(),
+    archive_ms() and accuse_ms() read the same stored floats after it as before, while audit_ms() now describes the
+    roll call's observer passes (its first three sum, in float, to rollcall_ms()[0] as they did to timeline_ms()[0])"""
+    from bftsim.runtime import Simulator
+    c = STREAMS["cfg1"]()
+    f32 = lambda ms: np.float32(ms[0]) + np.float32(ms[1]) + np.float32(ms[2])
+    sim = Simulator(c["cfg"])
+    try:
+        tr, H = _tr(c["stream"], c["off"], c["f0"]), c["heights"]
+        audit = sim.audit_trace(tr, max_heights=H)
+        _, archive = sim.archive_trace(tr, max_heights=H)
+        accuse = sim.accuse_trace(tr, max_heights=H)
+        tl = sim.timeline_trace(tr, max_heights=H)
+        before = sim.timeline_ms(), sim.archive_ms(), sim.accuse_ms()
+        audit_before = sim.audit_ms()
+        roll = sim.rollcall_trace(tr, max_heights=H)
+        after = sim.timeline_ms(), sim.archive_ms(), sim.accuse_ms()
+        audit_after, roll_ms = sim.audit_ms(), sim.rollcall_ms()
+    finally:
+        sim.close()
+    for got in (archive, accuse, tl, roll):
+        _same_audit(got.audit, audit)
+    _same_timeline(roll.timeline, tl)
+    print("ms", before, after, audit_before, audit_after, roll_ms)
+    assert after == before
+    assert len(roll_ms) == 6 and len(before[0]) == 4
+    assert f32(audit_before) == np.float32(before[0][0]) and f32(audit_after) == np.float32(roll_ms[0])
+    assert audit_after != audit_before
+
+
 def test_last_trace_equals_exported_and_leaves_the_run_alone():
     """rollcall_last_trace equals rollcall_trace(export_trace()) for a launch and for a sub-range, and the Python roll
     call on the reference trace; fetch() and the crypto_verify report are bit-identical before and after"""
