@@ -494,12 +494,56 @@ static hipError_t pmc_evict(bftsim* h, hipStream_t s) {
     return hipGetLastError();
 }
 
-static void use_set0_scratch(bftsim* h) {
-    // after a pipelined launch d_hist .. d_save point at that launch's set; set 0's are the handle's own
-    if (h->n_sets == 0 || !h->sets[0].hist) return;
-    bftsim::RowSet& r = h->sets[0];
-    h->d_hist = r.hist; h->d_rcs = r.rcs; h->d_backlog = r.backlog; h->d_resume = r.resume; h->d_save = r.save;
-    h->d_resume_q = r.resume_q;
+template <class T>
+static void dev_free(T*& p) {
+    (void)hipFree(p);
+    p = nullptr;
+}
+
+// workgroups of a consensus kernel over n instances: 64 / seg instances per wave, or one per workgroup
+static uint64_t launch_blocks(const bftsim* h, uint64_t n) {
+    const uint64_t per_block = h->seg > 64 ? 1 : 64 / h->seg;
+    return (n + per_block - 1) / per_block;
+}
+
+// A row-table set's device buffers for n instances; which ones depends on the mode alone (the configuration, the
+// window, sfx_rows, backlog_bytes, the number of sets), so every set of a handle has the same ones. The set's events
+// and its hint are not among them: they live as long as the handle.
+static int alloc_set(bftsim* h, bftsim::RowSet& r, uint64_t n) {
+    const bool n64 = h->seg == 64 && h->cfg.n == 64;
+    HIPCHECK(h, hipMalloc(&r.ch, n * 4));
+    HIPCHECK(h, hipMalloc(&r.flags, n * 4));
+    HIPCHECK(h, hipMalloc(&r.ticks, n * 4));
+    HIPCHECK(h, hipMalloc(&r.views, n * 8));
+    HIPCHECK(h, hipMalloc(&r.rec, n * h->hcap * 16));
+    HIPCHECK(h, hipMalloc(&r.hash, n * h->hcap * 32));
+    HIPCHECK(h, hipMalloc(&r.hist, bft::HIST_BINS * sizeof(uint64_t)));
+    HIPCHECK(h, hipMalloc(&r.rcs, launch_blocks(h, n) * bft::rcs_words(h->seg, h->rcs_k) * 4));
+    if (h->backlog_bytes) HIPCHECK(h, hipMalloc(&r.backlog, h->backlog_bytes));
+    if (n64) {                                         // FAST kernel hand-over buffers
+        HIPCHECK(h, hipMalloc(&r.resume, n * 4));
+        HIPCHECK(h, hipMalloc(&r.resume_q, (n + 2) * 4));
+        HIPCHECK(h, hipMalloc(&r.save, (uint64_t)bft::SAVE_WORDS * n * 64 * 4));
+    }
+    if (h->sfx_rows) {                                 // a hash pass (runs without in-kernel hashes): its suffix rows
+        HIPCHECK(h, hipMalloc(&r.sfx, (uint64_t)h->sfx_rows * n * bft::SFX_DEV_DW * 4ull));
+        if (n64 && h->n_sets >= 2 && h->sfx_rows >= h->cfg.heights) {   // predicted chains of pipelined FAST launches
+            HIPCHECK(h, hipMalloc(&r.byz, n * 8));                      // 
+            HIPCHECK(h, hipMalloc(&r.bad, n * 4));
+            HIPCHECK(h, hipMalloc(&r.pred, n * h->cfg.heights * 4ull));
+        }
+    } else if (n64 && !h->window) {
+        // little-endian seeds at N = 64: the seed chain's predicted blocks (DESIGN §4f)
+        HIPCHECK(h, hipMalloc(&r.spec, (uint64_t)(h->cfg.heights + 1u) * n * 4ull));
+    }
+    return BFTSIM_OK;
+}
+
+static void free_set(bftsim::RowSet& r) {
+    dev_free(r.ch); dev_free(r.flags); dev_free(r.ticks); dev_free(r.views); dev_free(r.rec); dev_free(r.hash);
+    dev_free(r.sfx); dev_free(r.spec); dev_free(r.byz); dev_free(r.bad); dev_free(r.pred);
+    dev_free(r.hist); dev_free(r.rcs); dev_free(r.backlog); dev_free(r.resume); dev_free(r.resume_q); dev_free(r.save);
+    r.busy = false;
 }
 
 static void trace_drop(bftsim* h) {
@@ -520,47 +564,19 @@ static void free_bufs(bftsim* h) {
     if (h->n_pend) (void)sync_all(h);
     h->n_pend = 0;
     h->last_pipe = false;
-    use_set0_scratch(h);
-    // the per-height row tables are owned by the sets (set 0 = the unpipelined tables); d_ch .. d_hash
-    // only point at the set of the last launch
-    if (h->n_sets == 0) {
-        (void)hipFree(h->d_ch); (void)hipFree(h->d_flags); (void)hipFree(h->d_ticks); (void)hipFree(h->d_views);
-        (void)hipFree(h->d_rec); (void)hipFree(h->d_hash);
-    }
-    for (uint32_t k = 0; k < h->n_sets; ++k) {
-        bftsim::RowSet& r = h->sets[k];
-        (void)hipFree(r.ch); (void)hipFree(r.flags); (void)hipFree(r.ticks); (void)hipFree(r.views);
-        (void)hipFree(r.rec); (void)hipFree(r.hash); (void)hipFree(r.sfx); (void)hipFree(r.spec);
-        (void)hipFree(r.byz); (void)hipFree(r.bad); (void)hipFree(r.pred);
-        if (k > 0) {                                   // set 0's scratch is the handle's own
-            (void)hipFree(r.hist); (void)hipFree(r.rcs); (void)hipFree(r.backlog); (void)hipFree(r.resume);
-            (void)hipFree(r.save); (void)hipFree(r.resume_q);
-        }
-        r.ch = r.flags = r.ticks = nullptr; r.views = nullptr; r.rec = nullptr; r.hash = nullptr; r.sfx = nullptr;
-        r.spec = nullptr; r.byz = nullptr; r.bad = nullptr; r.pred = nullptr;
-        r.hist = nullptr; r.rcs = r.backlog = r.resume = r.save = r.resume_q = nullptr;
-    }
-
-    (void)hipFree(h->d_trace); (void)hipFree(h->d_tips); (void)hipFree(h->d_rcs);
-    h->d_rcs = nullptr;
-    (void)hipFree(h->d_backlog);
-    h->d_backlog = nullptr;
-    (void)hipFree(h->d_mlog); (void)hipFree(h->d_mlog_n);
-    h->d_mlog = nullptr; h->d_mlog_n = nullptr;
-    (void)hipFree(h->d_vsnap); (void)hipFree(h->d_votes); (void)hipFree(h->d_vsig); (void)hipFree(h->d_vhas);
-    h->d_vsnap = nullptr; h->d_votes = nullptr; h->d_vsig = nullptr; h->d_vhas = nullptr; h->vsig_n = 0;
-    h->backlog_bytes = 0;
-    (void)hipFree(h->d_resume); (void)hipFree(h->d_save); (void)hipFree(h->d_resume_q);
-    h->d_resume = nullptr; h->d_save = nullptr; h->d_resume_q = nullptr;
-    for (uint32_t k = 0; k < bftsim::MAX_SETS; ++k) h->sets[k].busy = false;
+    for (uint32_t k = 0; k < h->n_sets; ++k) free_set(h->sets[k]);
     h->n_sets = 0;
     h->cur_set = 0;
-    h->d_ch = h->d_flags = h->d_ticks = nullptr; h->d_views = nullptr;
-    h->d_rec = nullptr; h->d_hash = nullptr; h->d_trace = nullptr; h->d_tips = nullptr;
+    dev_free(h->d_trace); dev_free(h->d_tips);
+    dev_free(h->d_mlog); dev_free(h->d_mlog_n);
+    dev_free(h->d_vsnap); dev_free(h->d_votes); dev_free(h->d_vsig); dev_free(h->d_vhas);
+    h->vsig_n = 0;
+    h->backlog_bytes = 0;
     h->cap_inst = 0;
     h->n_req = 0;
     h->last_n = 0;                    // nothing left to fetch: the buffers of the last launch are gone
     h->last_first = 0;
+    h->last_set = 0;
 }
 
 static int flush_batch(bftsim* h, bool final = false);
@@ -731,7 +747,6 @@ int bftsim_create(const bftsim_config* cfg, int hip_device, bftsim_t** out) {
     HIPCHECK(h, hipMalloc(&h->d_ghash, 32));
     HIPCHECK(h, hipMemcpy(h->d_ghash, h->genesis_hash, 32, hipMemcpyHostToDevice));
     HIPCHECK(h, hipMalloc(&h->d_stats, 16 * sizeof(unsigned long long)));
-    HIPCHECK(h, hipMalloc(&h->d_hist, bft::HIST_BINS * sizeof(uint64_t)));
     for (uint32_t i = 0; i < bftsim::RING; ++i) {
         HIPCHECK(h, hipEventCreate(&h->ring[i].c0)); HIPCHECK(h, hipEventCreate(&h->ring[i].c1));
         HIPCHECK(h, hipEventCreate(&h->ring[i].h0)); HIPCHECK(h, hipEventCreate(&h->ring[i].h1));
@@ -746,7 +761,7 @@ void bftsim_destroy(bftsim_t* h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
     free_bufs(h);
-    (void)hipFree(h->d_addr); (void)hipFree(h->d_ghash); (void)hipFree(h->d_stats); (void)hipFree(h->d_hist);
+    (void)hipFree(h->d_addr); (void)hipFree(h->d_ghash); (void)hipFree(h->d_stats);
     (void)hipFree(h->d_red);
     (void)hipFree(h->d_evict);
     (void)hipFree(h->d_keys);
@@ -774,7 +789,27 @@ void bftsim_destroy(bftsim_t* h) {
     delete h;
 }
 
-static bft::Params make_params(bftsim* h, uint64_t first, uint64_t n);
+// What a launch runs. It follows from the configuration and the handle's switches, never from the row-table set the
+// launch gets (every set has the same buffers, so set 0 answers for all):
+//   need_seed  the consensus kernel hashes each block itself (no hash pass): proposers depend on the hashes, or the
+//              rows are a ring (window);
+//   fast       FAST + resume for N = 64: big-endian seeds (proposer 0, hashes in the post-pass) or little-endian seeds
+//              (spec: the seed chain's predictions, else hashes in-kernel); not for windowed rows, traces or the opt-in
+//              modes;
+//   pipe       on the launch streams with a set of the ring; not with per-launch host state (traces, the crypto log,
+//              which the next calls read from the last launch alone).
+struct LaunchMode { bool need_seed, fast, spec, pipe; };
+static LaunchMode launch_mode(const bftsim* h) {
+    const bft::Params c = bft::params_from_config(h->cfg, h->seg, h->hcap, h->genesis_seed, 0, 1);
+    const bool mlog = h->crypto && h->d_mlog;          // one message at a time (make_params)
+    LaunchMode m;
+    m.need_seed = c.need_seed || h->window;
+    m.fast = h->fast && c.fast && !mlog && h->sets[0].save && !h->window && !h->h_trace && h->seg == 64 &&
+             h->cfg.n == 64;
+    m.spec = m.fast && m.need_seed && h->seed_spec && h->sets[0].spec;
+    m.pipe = h->pipeline >= 2 && (!m.need_seed || m.spec) && h->n_sets >= 2 && !h->h_trace && !mlog;
+    return m;
+}
 
 int bftsim_prepare(bftsim_t* h, uint64_t n) {
     if (!h || n == 0 || n > (1ull << 31)) return fail(h, BFTSIM_EINVAL, "bad instance count");
@@ -783,38 +818,13 @@ int bftsim_prepare(bftsim_t* h, uint64_t n) {
     if (n <= h->cap_inst) { h->n_req = n; return BFTSIM_OK; }
     if (h->last_n) if (int rc = sync_all(h)) return rc;   // the last launch may still use them
     free_bufs(h);
-    HIPCHECK(h, hipMalloc(&h->d_ch, n * 4));
-    HIPCHECK(h, hipMalloc(&h->d_flags, n * 4));
-    HIPCHECK(h, hipMalloc(&h->d_ticks, n * 4));
-    HIPCHECK(h, hipMalloc(&h->d_views, n * 8));
-    HIPCHECK(h, hipMalloc(&h->d_rec, n * h->hcap * 16));
-    HIPCHECK(h, hipMalloc(&h->d_hash, n * h->hcap * 32));
     HIPCHECK(h, hipMalloc(&h->d_tips, n * 32));
-    {
-        uint64_t per_block = h->seg > 64 ? 1 : 64 / h->seg;
-        uint64_t blocks = (n + per_block - 1) / per_block;
-        HIPCHECK(h, hipMalloc(&h->d_rcs, blocks * bft::rcs_words(h->seg, h->rcs_k) * 4));
-        if (h->crypto) {
-            HIPCHECK(h, hipMalloc(&h->d_mlog, n * (uint64_t)h->mlog_cap * bft::MLOG_WORDS * 4));
-            HIPCHECK(h, hipMalloc(&h->d_mlog_n, n * 4));
-            HIPCHECK(h, hipMalloc(&h->d_vsnap, n * (uint64_t)h->seg * 8 * 4));
-            HIPCHECK(h, hipMalloc(&h->d_votes, n * (uint64_t)h->hcap * 8 * 4));
-        }
-        if (h->cfg.backlog_mode == BFTSIM_BACKLOG_REPLAY) {
-            h->backlog_bytes = blocks * bft::backlog_words(h->seg) * 4;
-            HIPCHECK(h, hipMalloc(&h->d_backlog, h->backlog_bytes));
-        }
+    if (h->crypto) {
+        HIPCHECK(h, hipMalloc(&h->d_mlog, n * (uint64_t)h->mlog_cap * bft::MLOG_WORDS * 4));
+        HIPCHECK(h, hipMalloc(&h->d_mlog_n, n * 4));
+        HIPCHECK(h, hipMalloc(&h->d_vsnap, n * (uint64_t)h->seg * 8 * 4));
+        HIPCHECK(h, hipMalloc(&h->d_votes, n * (uint64_t)h->hcap * 8 * 4));
     }
-    if (h->seg == 64 && h->cfg.n == 64) {          // FAST kernel hand-over buffers
-        HIPCHECK(h, hipMalloc(&h->d_resume, n * 4));
-        HIPCHECK(h, hipMalloc(&h->d_resume_q, (n + 2) * 4));
-        HIPCHECK(h, hipMalloc(&h->d_save, (uint64_t)bft::SAVE_WORDS * n * 64 * 4));
-    }
-    h->sets[0].ch = h->d_ch; h->sets[0].flags = h->d_flags; h->sets[0].ticks = h->d_ticks;
-    h->sets[0].views = h->d_views; h->sets[0].rec = h->d_rec; h->sets[0].hash = h->d_hash;
-    h->sets[0].hist = h->d_hist; h->sets[0].rcs = h->d_rcs; h->sets[0].backlog = h->d_backlog;
-    h->sets[0].resume = h->d_resume; h->sets[0].save = h->d_save; h->sets[0].resume_q = h->d_resume_q;
-    h->n_sets = 1;
     // the switches of the tests and the A/B scripts, read only under BFTSIM_TESTING=1 (never the product path): a
     // 32-bit one clamped to [lo, hi], a 64-bit one as written; both say whether the variable was set
     const char* tst = getenv("BFTSIM_TESTING");
@@ -855,58 +865,32 @@ int bftsim_prepare(bftsim_t* h, uint64_t n) {
             HIPCHECK(h, hipMemset(h->d_evict, 0, EVICT_BYTES + 16));
         }
     }
-    const uint64_t per_block = h->seg > 64 ? 1 : 64 / h->seg, blocks = (n + per_block - 1) / per_block;
-    for (uint32_t k = 1; k < (uint32_t)h->pipeline; ++k) {
-        bftsim::RowSet& r = h->sets[k];
-        HIPCHECK(h, hipMalloc(&r.ch, n * 4));
-        HIPCHECK(h, hipMalloc(&r.flags, n * 4));
-        HIPCHECK(h, hipMalloc(&r.ticks, n * 4));
-        HIPCHECK(h, hipMalloc(&r.views, n * 8));
-        HIPCHECK(h, hipMalloc(&r.rec, n * h->hcap * 16));
-        HIPCHECK(h, hipMalloc(&r.hash, n * h->hcap * 32));
-        h->n_sets = k + 1;
-        {
-            HIPCHECK(h, hipMalloc(&r.hist, bft::HIST_BINS * sizeof(uint64_t)));
-            HIPCHECK(h, hipMalloc(&r.rcs, blocks * bft::rcs_words(h->seg, h->rcs_k) * 4));
-            if (h->d_backlog) HIPCHECK(h, hipMalloc(&r.backlog, h->backlog_bytes));
-            if (h->d_resume) {
-                HIPCHECK(h, hipMalloc(&r.resume, n * 4));
-                HIPCHECK(h, hipMalloc(&r.resume_q, (n + 2) * 4));
-                HIPCHECK(h, hipMalloc(&r.save, (uint64_t)bft::SAVE_WORDS * n * 64 * 4));
-            }
-        }
-    }
     // the hash pass's suffix rows (runs without in-kernel hashes): every height in one chunk up to 2 GiB
     // per set, fewer heights per chunk beyond
     h->sfx_rows = 0;
-    if (!make_params(h, 0, 1).need_seed) {
-        const uint64_t per_row = n * bft::SFX_DEV_DW * 4ull;
-        uint64_t rows = (2ull << 30) / per_row;
+    if (!launch_mode(h).need_seed) {
+        uint64_t rows = (2ull << 30) / (n * bft::SFX_DEV_DW * 4ull);
         if (rows < 1) rows = 1;
         if (rows > h->cfg.heights) rows = h->cfg.heights;
         if (sfx_cap > 0 && sfx_cap < rows) rows = sfx_cap;   // tests only (BFTSIM_SFX_ROWS)
         if (rows * n >= (1ull << 32)) rows = ((1ull << 32) - 1) / n;
         h->sfx_rows = (uint32_t)rows;
-        for (uint32_t k = 0; k < h->n_sets; ++k) HIPCHECK(h, hipMalloc(&h->sets[k].sfx, rows * per_row));
-        if (h->seg == 64 && h->cfg.n == 64 && h->n_sets >= 2 && rows >= h->cfg.heights)
-            for (uint32_t k = 0; k < h->n_sets; ++k) {   // predicted chains of pipelined FAST launches
-                HIPCHECK(h, hipMalloc(&h->sets[k].byz, n * 8));
-                HIPCHECK(h, hipMalloc(&h->sets[k].bad, n * 4));
-                HIPCHECK(h, hipMalloc(&h->sets[k].pred, n * h->cfg.heights * 4ull));
-            }
-        // every stream of the pipelined mode now, while the HIP runtime still has hardware queues of its own to
-        // give each (streams created later in a busy process can share one, which serializes their batches)
-        if (h->n_sets >= 2) {
-            for (uint32_t k = 0; k < h->n_cs && k < bftsim::MAX_CS; ++k)
-                if (!h->cs[k]) HIPCHECK(h, hipStreamCreateWithFlags(&h->cs[k], hipStreamNonBlocking));
-            const uint32_t nh = h->n_hs > bftsim::N_HS_SPEC ? h->n_hs : bftsim::N_HS_SPEC;
-            for (uint32_t k = 0; k < nh && k < bftsim::MAX_HS; ++k)
-                if (!h->hstr[k]) HIPCHECK(h, hipStreamCreateWithFlags(&h->hstr[k], hipStreamNonBlocking));
-        }
-    } else if (h->seg == 64 && h->cfg.n == 64 && !h->window) {
-        // little-endian seeds at N = 64: the seed chain's predicted blocks (DESIGN §4f)
-        for (uint32_t k = 0; k < h->n_sets; ++k)
-            HIPCHECK(h, hipMalloc(&h->sets[k].spec, (uint64_t)(h->cfg.heights + 1u) * n * 4ull));
+    }
+    if (h->cfg.backlog_mode == BFTSIM_BACKLOG_REPLAY)
+        h->backlog_bytes = launch_blocks(h, n) * bft::backlog_words(h->seg) * 4;
+    // the sets: one, or the ring of the pipelined mode. Counted before they are filled, so that a prepare that fails
+    // half-way leaves nothing that free_bufs does not find
+    h->n_sets = h->pipeline > 1 ? (uint32_t)h->pipeline : 1u;
+    for (uint32_t k = 0; k < h->n_sets; ++k)
+        if (int rc = alloc_set(h, h->sets[k], n)) return rc;
+    // every stream of the pipelined mode now, while the HIP runtime still has hardware queues of its own to
+    // give each (streams created later in a busy process can share one, which serializes their batches)
+    if (h->sfx_rows && h->n_sets >= 2) {
+        for (uint32_t k = 0; k < h->n_cs && k < bftsim::MAX_CS; ++k)
+            if (!h->cs[k]) HIPCHECK(h, hipStreamCreateWithFlags(&h->cs[k], hipStreamNonBlocking));
+        const uint32_t nh = h->n_hs > bftsim::N_HS_SPEC ? h->n_hs : bftsim::N_HS_SPEC;
+        for (uint32_t k = 0; k < nh && k < bftsim::MAX_HS; ++k)
+            if (!h->hstr[k]) HIPCHECK(h, hipStreamCreateWithFlags(&h->hstr[k], hipStreamNonBlocking));
     }
     h->cap_inst = n;
     h->n_req = n;
@@ -950,25 +934,28 @@ int bftsim_set_trace(bftsim_t* h, uint64_t* host_out, uint32_t trace_ticks) {
     return BFTSIM_OK;
 }
 
-static bft::Params make_params(bftsim* h, uint64_t first, uint64_t n) {
+// The launch parameters of instances [first, first + n) on row-table set r. Whatever reads a launch's results builds
+// them again over the last launch's set. The FAST kernels' hand-over fields are not filled here: only a FAST launch
+// has them (run_consensus).
+static bft::Params make_params(bftsim* h, const bftsim::RowSet& r, uint64_t first, uint64_t n) {
     bft::Params p = bft::params_from_config(h->cfg, h->seg, h->hcap, h->genesis_seed, first, n);
     p.addresses = h->d_addr;
     p.genesis_hash = h->d_ghash;
-    p.committed_height = h->d_ch;
-    p.flags = h->d_flags;
-    p.ticks = h->d_ticks;
-    p.views = h->d_views;
-    p.rec = h->d_rec;
-    p.hash = h->d_hash;
+    p.committed_height = r.ch;
+    p.flags = r.flags;
+    p.ticks = r.ticks;
+    p.views = r.views;
+    p.rec = r.rec;
+    p.hash = r.hash;
     p.trace = h->d_trace;
     p.trace_ticks = h->trace_ticks;
-    p.hist = h->d_hist;
-    p.rcs = h->d_rcs;
+    p.hist = r.hist;
+    p.rcs = r.rcs;
     p.rcs_k = h->rcs_k;
     p.chain_prio = bftsim::PRIO_RECORDED;
     p.chain_grid = h->chain_grid;
     p.chain_inline = h->chain_inline;
-    p.backlog = h->d_backlog;
+    p.backlog = r.backlog;
     if (h->crypto && h->d_mlog) {
         p.mlog = h->d_mlog;
         p.mlog_n = h->d_mlog_n;
@@ -994,9 +981,177 @@ static uint32_t chain_kind(const bftsim* h, uint64_t n, bool spec) {
     return bft::CHAIN_KERNEL_PAIR;
 }
 
+// predicted chains are for lossless schedules (no drops, no proposer crashes), where the canonical tick
+// commits every height; with drops most instances leave it early and the predicted chains would mostly be repaired
+// (drop64: 22.6 ms of chain kernels per launch against 0.7)
+static bool predictable(const bftsim* h, const bft::Params& p) {
+    return (p.thr16 == 0 && p.crash_on == 0) || h->spec_lossy;
+}
+
 static uint32_t clear_blocks(uint64_t n_rec) {   // bft_clear_kernel's grid: grid-stride, at least one block
     const uint64_t b = (n_rec + 255u) / 256u;
     return (uint32_t)(b < 1 ? 1 : b > 4096 ? 4096 : b);
+}
+
+// a launch's kernel times into the sums that bftsim_kernel_ms_sum reports, once its kernels are done
+static int fold_ev(bftsim* h, bftsim::LaunchEv& ev) {
+    HIPCHECK(h, hipEventSynchronize(ev.has_hash ? ev.h1 : ev.c1));
+    float a = 0, b = 0;
+    HIPCHECK(h, hipEventElapsedTime(&a, ev.c0, ev.c1));
+    if (ev.has_hash) HIPCHECK(h, hipEventElapsedTime(&b, ev.h0, ev.h1));
+    h->acc_c += a; h->acc_h += b; h->acc_n += 1;
+    ev.pending = false;
+    return BFTSIM_OK;
+}
+
+// stream t's work so far is the last that uses the set: its next launch waits for it
+static int set_done(bftsim* h, bftsim::RowSet& r, hipStream_t t) {
+    HIPCHECK(h, hipEventRecord(r.done, t));
+    r.batch_done = nullptr;
+    r.busy = true;
+    return BFTSIM_OK;
+}
+
+// A launch, step 1: its row-table set and its stream. Unpipelined: set 0 on the caller's stream s, once the pipelined
+// launches before it are done (they may still use set 0); the ring's cursor stays. Pipelined: the next set in the
+// ring, once its last launch's chains are done (a launch of it still waiting in the hash batch is flushed first), on
+// the next launch stream, after the caller's earlier work on s.
+static int choose_set(bftsim* h, const LaunchMode& m, hipStream_t& s, uint32_t& set) {
+    set = 0;
+    if (!m.pipe) {
+        if (h->last_pipe) {
+            if (int rc = sync_all(h)) return rc;
+            h->last_pipe = false;
+        }
+        return BFTSIM_OK;
+    }
+    set = h->cur_set = (h->cur_set + 1) % h->n_sets;
+    for (uint32_t i = 0; i < h->n_pend; ++i)
+        if (h->pend[i].set == set) { if (int rc = flush_batch(h)) return rc; break; }
+    bftsim::RowSet& r = h->sets[set];
+    if (!r.entry) HIPCHECK(h, hipEventCreateWithFlags(&r.entry, hipEventDisableTiming));
+    HIPCHECK(h, hipEventRecord(r.entry, s));
+    h->cur_cs = (h->cur_cs + 1) % (m.spec ? bftsim::N_CS_SEEDED : h->n_cs);
+    if (!h->cs[h->cur_cs]) HIPCHECK(h, hipStreamCreateWithFlags(&h->cs[h->cur_cs], hipStreamNonBlocking));
+    s = h->cs[h->cur_cs];
+    HIPCHECK(h, hipStreamWaitEvent(s, r.entry, 0));
+    if (r.busy) HIPCHECK(h, hipStreamWaitEvent(s, r.batch_done ? r.batch_done : r.done, 0));
+    h->last_pipe = true;
+    return BFTSIM_OK;
+}
+
+// Step 2: the set's state zeroed, then the consensus kernels on stream s, between the launch's events c0 and c1
+static int run_consensus(bftsim* h, const LaunchMode& m, bftsim::RowSet& r, hipStream_t s, bftsim::LaunchEv& ev,
+                         bft::Params& p) {
+    const uint64_t n = p.n_instances;
+    // the histogram and (FAST launches) the hand-over flags and queue zeroed by one dispatch; the record rows too,
+    // except for FAST launches: the FAST and resume bodies read a row only once they have recorded it (canon_blk,
+    // canon_seed, refresh_tip_from_table: rows <= the canonical height), and every reader after the launch stops at
+    // the committed height (fetch, export, tips, chains, the predicted chains' check) -- 43 MB of writes per cfg3
+    // launch saved
+    const uint64_t n_rec = m.fast ? 0 : n * h->hcap;
+    hipLaunchKernelGGL(bft_clear_kernel, dim3(clear_blocks(n_rec > n ? n_rec : n)), dim3(256), 0, s, (uint4*)r.rec,
+                       n_rec, r.hist, m.fast ? r.resume : nullptr, (uint32_t)n, m.fast ? r.resume_q : nullptr);
+    HIPCHECK(h, hipGetLastError());
+    if (r.backlog) HIPCHECK(h, hipMemsetAsync(r.backlog, 0, h->backlog_bytes, s));
+    const dim3 grid((uint32_t)launch_blocks(h, n));
+    const size_t lds = bft::lds_bytes(h->seg, p.need_seed != 0);
+    HIPCHECK(h, hipEventRecord(ev.c0, s));
+    if (m.fast) {
+        // FAST kernel over every instance, then the full kernel over the ones it handed over
+        p.resume_flags = r.resume;
+        p.resume_q = r.resume_q;
+        p.save = r.save;
+        p.save_stride = n * 64;
+        if (!r.hint) {
+            HIPCHECK(h, hipHostMalloc((void**)&r.hint, 4, hipHostMallocMapped | hipHostMallocCoherent));
+            *r.hint = 0xffffffffu;                    // unknown: the full grid, or another set's last count
+            for (uint32_t k = 0; k < h->n_sets; ++k)  // (the grid only paces the persistent waves)
+                if (h->sets[k].hint && &h->sets[k] != &r && *h->sets[k].hint != 0xffffffffu) {
+                    *r.hint = __atomic_load_n(h->sets[k].hint, __ATOMIC_RELAXED);
+                    break;
+                }
+        }
+        p.resume_hint = r.hint;
+        if (m.spec) {                                    // the predicted blocks first (little-endian seeds)
+            p.spec = r.spec;
+            HIPCHECK(h, bft::launch_seed_chain((uint32_t)n, s, p));
+            HIPCHECK(h, pmc_evict(h, s));
+        }
+        HIPCHECK(h, bft::launch_fast(grid, s, p));
+        HIPCHECK(h, pmc_evict(h, s));
+        HIPCHECK(h, bft::launch_resume(grid, lds, s, p));
+        HIPCHECK(h, pmc_evict(h, s));
+    } else {
+        const bool ext = p.backlog_replay || p.mlog;   // the opt-in modes' kernel build (MODE_EXT)
+        HIPCHECK(h, bft::launch_general(p.need_seed != 0, ext, h->seg, grid, lds, s, p));
+        HIPCHECK(h, pmc_evict(h, s));
+    }
+    HIPCHECK(h, hipEventRecord(ev.c1, s));
+    ev.has_hash = !p.need_seed;
+    ev.pending = true;
+    return BFTSIM_OK;
+}
+
+// Step 3 (runs without in-kernel hashes): the launch's hash pass, or its place in the batch whose chains one kernel
+// runs (flush_batch). s: the launch's stream; ev: its events, the ring's last
+static int run_hash_pass(bftsim* h, const LaunchMode& m, uint32_t set, hipStream_t s, bftsim::LaunchEv& ev,
+                         const bft::Params& p, uint64_t first) {
+    bftsim::RowSet& r = h->sets[set];
+    const uint64_t n = p.n_instances;
+    const uint32_t H = h->cfg.heights, K = h->sfx_rows;
+    // Where the suffix rows go depends on how long the consensus kernel runs against the chains
+    // (A/B, profiles/r03/ab_sfx): the N = 64 FAST kernel is short, so a full-chip pass by a thread per
+    // (instance, height) runs on the launch stream right behind it; the general kernels run far longer
+    // than the chains, so a thread per instance over its heights runs on the hash stream beside them.
+    if (m.pipe && K >= H && m.fast) {
+        // big-endian seeds: predicted chains
+        const bool hspec = r.byz && n < h->hash_spec_max && predictable(h, p);
+        if (!hspec) {
+            // suffix rows now (unless the lane chains encode them); the chains in the next batch (flush_batch)
+            if (!(h->chain_inline && chain_kind(h, n, false) == bft::CHAIN_KERNEL_LANE)) {
+                HIPCHECK(h, bft::launch_hash_suffix((uint32_t)n, 1, K, r.sfx, false, s, p));
+                HIPCHECK(h, pmc_evict(h, s));
+            }
+            HIPCHECK(h, hipEventRecord(ev.sx, s));
+        }
+        ev.has_hash = false;                          // the batch's last launch carries the chain time
+        // one chain kernel runs every pending launch with the batch's sizes (suffix-row stride, grid):
+        // a launch of another size starts a batch of its own
+        if (h->n_pend > 0 && (h->batch_p.n_instances != p.n_instances || h->batch_spec != hspec))
+            if (int rc = flush_batch(h)) return rc;
+        if (h->n_pend == 0) {
+            h->batch_p = p;
+            h->batch_spec = hspec;
+            h->cur_hs = (h->cur_hs + 1) % (hspec ? bftsim::N_HS_SPEC : h->n_hs);   // the batch's hash stream
+            if (!h->hstr[h->cur_hs]) HIPCHECK(h, hipStreamCreateWithFlags(&h->hstr[h->cur_hs], hipStreamNonBlocking));
+            h->batch_hs = h->cur_hs;
+        }
+        h->pend[h->n_pend++] = {set, (h->ring_head - 1) % bftsim::RING, (uint32_t)first, h->cur_cs};
+        if (h->n_pend >= h->hash_batch) return flush_batch(h);
+        return BFTSIM_OK;
+    }
+    // one launch's hash pass: on a hash stream (pipelined) or the launch stream; chunks of K heights
+    // share the suffix rows (suffix and chain kernels in order on one stream)
+    hipStream_t t = s;
+    if (m.pipe) {
+        h->cur_hs = (h->cur_hs + 1) % h->n_hs;
+        if (!h->hstr[h->cur_hs]) HIPCHECK(h, hipStreamCreateWithFlags(&h->hstr[h->cur_hs], hipStreamNonBlocking));
+        t = h->hstr[h->cur_hs];
+        HIPCHECK(h, hipStreamWaitEvent(t, ev.c1, 0));
+    }
+    HIPCHECK(h, hipEventRecord(ev.h0, t));
+    const uint32_t kind = chain_kind(h, n, false);
+    for (uint32_t x0 = 1; x0 <= H; x0 += K) {
+        if (!(h->chain_inline && kind == bft::CHAIN_KERNEL_LANE)) {
+            HIPCHECK(h, bft::launch_hash_suffix((uint32_t)n, x0, K, r.sfx, !m.fast, t, p));
+            HIPCHECK(h, pmc_evict(h, t));
+        }
+        HIPCHECK(h, bft::launch_hash_chain((uint32_t)n, x0, K, r.sfx, kind, t, p));
+        HIPCHECK(h, pmc_evict(h, t));
+    }
+    HIPCHECK(h, hipEventRecord(ev.h1, t));
+    return m.pipe ? set_done(h, r, t) : BFTSIM_OK;
 }
 
 int bftsim_launch(bftsim_t* h, uint64_t first, void* stream) {
@@ -1015,196 +1170,39 @@ int bftsim_launch(bftsim_t* h, uint64_t first, void* stream) {
         HIPCHECK(h, hipMalloc(&h->d_trace, tb));
         HIPCHECK(h, hipMemsetAsync(h->d_trace, 0, tb, s));
     }
-    bft::Params p = make_params(h, first, n);
-    // pipelined: on the launch streams with the set's own scratch; not with per-launch host state (traces,
-    // the crypto log, which the next calls read from the last launch alone)
-    // FAST + resume for N = 64: big-endian seeds (proposer 0, hashes in the post-pass) or little-endian
-    // seeds (SEEDED: the seed chain's predictions, else hashes in-kernel); not for windowed rows, traces or
-    // the opt-in modes
-    const bool fast = h->fast && p.fast && !p.mlog && h->d_save && !h->window && !h->h_trace && h->seg == 64 &&
-                      h->cfg.n == 64;
-    const bool fast_launch = fast;
-    const bool spec = fast && p.need_seed && h->seed_spec && h->sets[0].spec;
-    const bool pipe = h->pipeline >= 2 && (!p.need_seed || spec) && h->n_sets >= 2 && !h->h_trace && !p.mlog;
-    if (h->last_pipe && !pipe) {
-        // a launch on the caller's stream after pipelined ones: they may still use set 0's scratch
-        if (int rc = sync_all(h)) return rc;
-        h->last_pipe = false;
-    }
-    use_set0_scratch(h);
-    p = make_params(h, first, n);
 #ifdef BFT_STAMPS
-    {
+    {   // on the caller's stream, ahead of the launch's entry event
         static uint64_t* d_st = nullptr;
         static uint64_t cap = 0;
-        uint64_t per = h->seg > 64 ? 1 : 64 / h->seg;
-        uint64_t waves = (n + per - 1) / per;
+        uint64_t waves = launch_blocks(h, n);
         if (waves > cap) { (void)hipFree(d_st); HIPCHECK(h, hipMalloc(&d_st, waves * 8 * bft::NSTAMP)); cap = waves; }
         HIPCHECK(h, hipMemsetAsync(d_st, 0, waves * 8 * bft::NSTAMP, s));
-        p.stamps = d_st;
         g_stamps = d_st;
         g_stamp_waves = waves;
     }
 #endif
-    if (pipe) {
-        // the next row-table set in the ring, once its last launch's chains are done (a launch of it still
-        // waiting in the hash batch is flushed first)
-        h->cur_set = (h->cur_set + 1) % h->n_sets;
-        for (uint32_t i = 0; i < h->n_pend; ++i)
-            if (h->pend[i].set == h->cur_set) { if (int rc = flush_batch(h)) return rc; break; }
-        bftsim::RowSet& r = h->sets[h->cur_set];
-        if (!r.entry) HIPCHECK(h, hipEventCreateWithFlags(&r.entry, hipEventDisableTiming));
-        HIPCHECK(h, hipEventRecord(r.entry, s));
-        h->cur_cs = (h->cur_cs + 1) % (spec ? bftsim::N_CS_SEEDED : h->n_cs);
-        if (!h->cs[h->cur_cs]) HIPCHECK(h, hipStreamCreateWithFlags(&h->cs[h->cur_cs], hipStreamNonBlocking));
-        hipStream_t ls = h->cs[h->cur_cs];
-        HIPCHECK(h, hipStreamWaitEvent(ls, r.entry, 0));
-        if (r.busy) HIPCHECK(h, hipStreamWaitEvent(ls, r.batch_done ? r.batch_done : r.done, 0));
-        s = ls;
-        h->d_hist = r.hist; h->d_rcs = r.rcs; h->d_backlog = r.backlog; h->d_resume = r.resume; h->d_save = r.save;
-        h->d_resume_q = r.resume_q;
-        p.hist = r.hist; p.rcs = r.rcs; p.backlog = r.backlog;
-        h->d_ch = r.ch; h->d_flags = r.flags; h->d_ticks = r.ticks; h->d_views = r.views;
-        h->d_rec = r.rec; h->d_hash = r.hash;
-        p.committed_height = h->d_ch; p.flags = h->d_flags; p.ticks = h->d_ticks; p.views = h->d_views;
-        p.rec = h->d_rec; p.hash = h->d_hash;
-        h->last_pipe = true;
-    }
+    const LaunchMode m = launch_mode(h);
+    uint32_t set = 0;
+    if (int rc = choose_set(h, m, s, set)) return rc;
+    bftsim::RowSet& r = h->sets[set];
+    bft::Params p = make_params(h, r, first, n);
+#ifdef BFT_STAMPS
+    p.stamps = g_stamps;
+#endif
     bftsim::LaunchEv& ev = h->ring[h->ring_head % bftsim::RING];
-    if (ev.pending) {                                    // 64 launches unread: fold the oldest in
-        HIPCHECK(h, hipEventSynchronize(ev.has_hash ? ev.h1 : ev.c1));
-        float a = 0, b = 0;
-        HIPCHECK(h, hipEventElapsedTime(&a, ev.c0, ev.c1));
-        if (ev.has_hash) HIPCHECK(h, hipEventElapsedTime(&b, ev.h0, ev.h1));
-        h->acc_c += a; h->acc_h += b; h->acc_n += 1;
-        ev.pending = false;
-    }
+    if (ev.pending) if (int rc = fold_ev(h, ev)) return rc;   // 64 launches unread: fold the oldest in
     h->ring_head += 1;
-    // the histogram and (FAST launches) the hand-over flags and queue zeroed by one dispatch; the record rows too,
-    // except for FAST launches: the FAST and resume bodies read a row only once they have recorded it (canon_blk,
-    // canon_seed, refresh_tip_from_table: rows <= the canonical height), and every reader after the launch stops at
-    // the committed height (fetch, export, tips, chains, the predicted chains' check) -- 43 MB of writes per cfg3
-    // launch saved
-    const bool clear_rec = !fast_launch;
-    const uint64_t n_rec = clear_rec ? (uint64_t)n * h->hcap : 0;
-    hipLaunchKernelGGL(bft_clear_kernel, dim3(clear_blocks(n_rec > n ? n_rec : n)), dim3(256), 0, s, (uint4*)h->d_rec,
-                       n_rec, h->d_hist, fast_launch ? h->d_resume : nullptr, (uint32_t)n,
-                       fast_launch ? h->d_resume_q : nullptr);
-    HIPCHECK(h, hipGetLastError());
-    if (h->d_backlog) HIPCHECK(h, hipMemsetAsync(h->d_backlog, 0, h->backlog_bytes, s));
-    uint32_t per_block = h->seg > 64 ? 1u : 64u / h->seg;      // instances per workgroup
-    uint32_t grid = (uint32_t)((n + per_block - 1) / per_block);
-    size_t lds = bft::lds_bytes(h->seg, p.need_seed != 0);
-    const bool ext = p.backlog_replay || p.mlog;       // the opt-in modes' kernel build (MODE_EXT)
-    HIPCHECK(h, hipEventRecord(ev.c0, s));
-    if (fast) {
-        // FAST kernel over every instance, then the full kernel over the ones it handed over
-        p.resume_flags = h->d_resume;
-        p.resume_q = h->d_resume_q;
-        p.save = h->d_save;
-        p.save_stride = n * 64;
-        {
-            bftsim::RowSet& r = h->sets[pipe ? h->cur_set : 0];
-            if (!r.hint) {
-                HIPCHECK(h, hipHostMalloc((void**)&r.hint, 4, hipHostMallocMapped | hipHostMallocCoherent));
-                *r.hint = 0xffffffffu;                    // unknown: the full grid, or another set's last count
-                for (uint32_t k = 0; k < h->n_sets; ++k)  // (the grid only paces the persistent waves)
-                    if (h->sets[k].hint && &h->sets[k] != &r && *h->sets[k].hint != 0xffffffffu) {
-                        *r.hint = __atomic_load_n(h->sets[k].hint, __ATOMIC_RELAXED);
-                        break;
-                    }
-            }
-            p.resume_hint = r.hint;
-        }
-        if (spec) {                                      // the predicted blocks first (little-endian seeds)
-            p.spec = h->sets[pipe ? h->cur_set : 0].spec;
-            HIPCHECK(h, bft::launch_seed_chain((uint32_t)n, s, p));
-            HIPCHECK(h, pmc_evict(h, s));
-        }
-        HIPCHECK(h, bft::launch_fast(dim3(grid), s, p));
-        HIPCHECK(h, pmc_evict(h, s));
-        HIPCHECK(h, bft::launch_resume(dim3(grid), lds, s, p));
-        HIPCHECK(h, pmc_evict(h, s));
-    } else {
-        HIPCHECK(h, bft::launch_general(p.need_seed != 0, ext, h->seg, dim3(grid), lds, s, p));
-        HIPCHECK(h, pmc_evict(h, s));
-    }
-    HIPCHECK(h, hipEventRecord(ev.c1, s));
-    ev.has_hash = !p.need_seed;
-    ev.pending = true;
-    if (!p.need_seed) {
-        uint32_t* sfx = h->sets[pipe ? h->cur_set : 0].sfx;
-        const uint32_t H = h->cfg.heights, K = h->sfx_rows;
-        // Where the suffix rows go depends on how long the consensus kernel runs against the chains
-        // (A/B, profiles/r03/ab_sfx): the N = 64 FAST kernel is short, so a full-chip pass by a thread per
-        // (instance, height) runs on the launch stream right behind it; the general kernels run far longer
-        // than the chains, so a thread per instance over its heights runs on the hash stream beside them.
-        const bool on_launch = fast;
-        if (pipe && K >= H && on_launch) {
-            bftsim::RowSet& r = h->sets[h->cur_set];
-            // big-endian seeds: predicted chains, for lossless schedules (no drops, no proposer crashes),
-            // where the canonical tick commits every height; with drops most instances leave it early and the
-            // predicted chains would mostly be repaired (drop64: 22.6 ms of chain kernels per launch against 0.7)
-            const bool hspec = r.byz && n < h->hash_spec_max && ((p.thr16 == 0 && p.crash_on == 0) || h->spec_lossy);
-            if (!hspec) {
-                // suffix rows now (unless the lane chains encode them); the chains in the next batch (flush_batch)
-                if (!(h->chain_inline && chain_kind(h, n, false) == bft::CHAIN_KERNEL_LANE)) {
-                    HIPCHECK(h, bft::launch_hash_suffix((uint32_t)n, 1, K, sfx, false, s, p));
-                    HIPCHECK(h, pmc_evict(h, s));
-                }
-                HIPCHECK(h, hipEventRecord(ev.sx, s));
-            }
-            ev.has_hash = false;                          // the batch's last launch carries the chain time
-            // one chain kernel runs every pending launch with the batch's sizes (suffix-row stride, grid):
-            // a launch of another size starts a batch of its own
-            if (h->n_pend > 0 && (h->batch_p.n_instances != p.n_instances || h->batch_spec != hspec))
-                if (int rc = flush_batch(h)) return rc;
-            if (h->n_pend == 0) {
-                h->batch_p = p;
-                h->batch_spec = hspec;
-                h->cur_hs = (h->cur_hs + 1) % (hspec ? bftsim::N_HS_SPEC : h->n_hs);   // the batch's hash stream
-                if (!h->hstr[h->cur_hs]) HIPCHECK(h, hipStreamCreateWithFlags(&h->hstr[h->cur_hs], hipStreamNonBlocking));
-                h->batch_hs = h->cur_hs;
-            }
-            h->pend[h->n_pend++] = {h->cur_set, (h->ring_head - 1) % bftsim::RING, (uint32_t)first, h->cur_cs};
-            if (h->n_pend >= h->hash_batch) if (int rc = flush_batch(h)) return rc;
-        } else {
-            // one launch's hash pass: on a hash stream (pipelined) or the launch stream; chunks of K heights
-            // share the suffix rows (suffix and chain kernels in order on one stream)
-            hipStream_t t = s;
-            if (pipe) {
-                h->cur_hs = (h->cur_hs + 1) % h->n_hs;
-                if (!h->hstr[h->cur_hs]) HIPCHECK(h, hipStreamCreateWithFlags(&h->hstr[h->cur_hs], hipStreamNonBlocking));
-                t = h->hstr[h->cur_hs];
-                HIPCHECK(h, hipStreamWaitEvent(t, ev.c1, 0));
-            }
-            HIPCHECK(h, hipEventRecord(ev.h0, t));
-            const uint32_t kind = chain_kind(h, n, false);
-            for (uint32_t x0 = 1; x0 <= H; x0 += K) {
-                if (!(h->chain_inline && kind == bft::CHAIN_KERNEL_LANE)) {
-                    HIPCHECK(h, bft::launch_hash_suffix((uint32_t)n, x0, K, sfx, !on_launch, t, p));
-                    HIPCHECK(h, pmc_evict(h, t));
-                }
-                HIPCHECK(h, bft::launch_hash_chain((uint32_t)n, x0, K, sfx, kind, t, p));
-                HIPCHECK(h, pmc_evict(h, t));
-            }
-            HIPCHECK(h, hipEventRecord(ev.h1, t));
-            if (pipe) {
-                HIPCHECK(h, hipEventRecord(h->sets[h->cur_set].done, t));
-                h->sets[h->cur_set].batch_done = nullptr;
-                h->sets[h->cur_set].busy = true;
-            }
-        }
-    }
-    if (pipe && p.need_seed) {                          // no hash pass: the set is free once this launch is done
-        HIPCHECK(h, hipEventRecord(h->sets[h->cur_set].done, s));
-        h->sets[h->cur_set].batch_done = nullptr;
-        h->sets[h->cur_set].busy = true;
+    if (int rc = run_consensus(h, m, r, s, ev, p)) return rc;
+    if (!m.need_seed) {
+        if (int rc = run_hash_pass(h, m, set, s, ev, p, first)) return rc;
+    } else if (m.pipe) {                                // no hash pass: the set is free once this launch is done
+        if (int rc = set_done(h, r, s)) return rc;
     }
     h->last_n = n;
     h->vsig_n = 0;
     trace_drop(h);
     h->last_first = first;
+    h->last_set = set;
     h->last_stream = s;
     return BFTSIM_OK;
 }
@@ -1218,8 +1216,7 @@ static int flush_batch(bftsim* h, bool final) {
     // start once the last launch's consensus kernel is done and take ~2 ms) runs as predicted lane-pair chains
     // instead: they start now, beside the launches' consensus kernels, and only the check and the repairs are left
     // behind them. With predictions on (the default) every batch is predicted already (§4j).
-    const bool conv = final && !h->batch_spec && h->sets[h->pend[0].set].byz != nullptr &&
-                      ((h->batch_p.thr16 == 0 && h->batch_p.crash_on == 0) || h->spec_lossy);   // lossless (launch)
+    const bool conv = final && !h->batch_spec && h->sets[h->pend[0].set].byz != nullptr && predictable(h, h->batch_p);
     const bool spec = h->batch_spec || conv;
     bft::ChainSets cs{};
     cs.count = h->n_pend;
@@ -1325,13 +1322,7 @@ int bftsim_kernel_ms_sum(bftsim_t* h, double* consensus_ms, double* hash_ms, uin
     if (int rc = flush_batch(h)) return rc;           // a pending batch's chain time goes to its last launch
     for (uint32_t i = 0; i < bftsim::RING; ++i) {
         bftsim::LaunchEv& ev = h->ring[i];
-        if (!ev.pending) continue;
-        HIPCHECK(h, hipEventSynchronize(ev.has_hash ? ev.h1 : ev.c1));
-        float a = 0, b = 0;
-        HIPCHECK(h, hipEventElapsedTime(&a, ev.c0, ev.c1));
-        if (ev.has_hash) HIPCHECK(h, hipEventElapsedTime(&b, ev.h0, ev.h1));
-        h->acc_c += a; h->acc_h += b; h->acc_n += 1;
-        ev.pending = false;
+        if (ev.pending) if (int rc = fold_ev(h, ev)) return rc;
     }
     if (consensus_ms) *consensus_ms = h->acc_c;
     if (hash_ms) *hash_ms = h->acc_h;
@@ -1363,7 +1354,7 @@ int bftsim_last_kernel_ms(bftsim_t* h, float* cms, float* hms) {
 // the fetch family writes one row per launched instance into caller buffers: refuse a short buffer
 // before anything is written (include/bftsim.h bftsim_launched_count)
 static int check_launched(bftsim* h, uint64_t capacity, const char* what) {
-    if (h->last_n == 0 || !h->d_ch) return fail(h, BFTSIM_EINVAL, std::string(what) + ": nothing launched");
+    if (h->last_n == 0) return fail(h, BFTSIM_EINVAL, std::string(what) + ": nothing launched");
     if (capacity < h->last_n)
         return fail(h, BFTSIM_EINVAL, std::string(what) + ": buffers hold " + std::to_string(capacity) +
                                           " instances, the last launch has " + std::to_string(h->last_n));
@@ -1373,7 +1364,7 @@ static int check_launched(bftsim* h, uint64_t capacity, const char* what) {
 int bftsim_launched_count(bftsim_t* h, uint64_t* first, uint64_t* n) {
     if (!h) return BFTSIM_EINVAL;
     if (first) *first = h->last_n ? h->last_first : 0;
-    if (n) *n = h->d_ch ? h->last_n : 0;
+    if (n) *n = h->last_n;
     return BFTSIM_OK;
 }
 
@@ -1382,18 +1373,19 @@ int bftsim_fetch(bftsim_t* h, bftsim_result* out) {
     if (h->window) return fail(h, BFTSIM_EINVAL, "windowed run: per-height rows are not kept (bftsim_fetch_summary)");
     if (int rc = check_launched(h, out->capacity, "bftsim_fetch")) return rc;
     if (int rc = sync_all(h)) return rc;
+    const bftsim::RowSet& r = h->sets[h->last_set];
     uint64_t n = h->last_n;
     uint32_t H = h->cfg.heights, hc = h->hcap;
     std::vector<uint32_t> ch32(n);
-    HIPCHECK(h, hipMemcpy(ch32.data(), h->d_ch, n * 4, hipMemcpyDeviceToHost));
+    HIPCHECK(h, hipMemcpy(ch32.data(), r.ch, n * 4, hipMemcpyDeviceToHost));
     for (uint64_t i = 0; i < n; ++i) out->committed_height[i] = ch32[i];
-    HIPCHECK(h, hipMemcpy(out->flags, h->d_flags, n * 4, hipMemcpyDeviceToHost));
-    HIPCHECK(h, hipMemcpy(out->ticks, h->d_ticks, n * 4, hipMemcpyDeviceToHost));
-    HIPCHECK(h, hipMemcpy(out->views, h->d_views, n * 8, hipMemcpyDeviceToHost));
+    HIPCHECK(h, hipMemcpy(out->flags, r.flags, n * 4, hipMemcpyDeviceToHost));
+    HIPCHECK(h, hipMemcpy(out->ticks, r.ticks, n * 4, hipMemcpyDeviceToHost));
+    HIPCHECK(h, hipMemcpy(out->views, r.views, n * 8, hipMemcpyDeviceToHost));
     std::vector<uint32_t> rec(n * hc * 4);
     std::vector<uint8_t> hs(n * hc * 32);
-    HIPCHECK(h, hipMemcpy(rec.data(), h->d_rec, rec.size() * 4, hipMemcpyDeviceToHost));
-    HIPCHECK(h, hipMemcpy(hs.data(), h->d_hash, hs.size(), hipMemcpyDeviceToHost));
+    HIPCHECK(h, hipMemcpy(rec.data(), r.rec, rec.size() * 4, hipMemcpyDeviceToHost));
+    HIPCHECK(h, hipMemcpy(hs.data(), r.hash, hs.size(), hipMemcpyDeviceToHost));
     for (uint64_t i = 0; i < n; ++i) {
         uint32_t ch = out->committed_height[i];
         for (uint32_t x = 1; x <= H; ++x) {
@@ -1421,7 +1413,7 @@ int bftsim_export_headers(bftsim_t* h, uint64_t capacity, uint8_t* hdr, uint32_t
     if (int rc = check_launched(h, capacity, "bftsim_export_headers")) return rc;
     if (int rc = sync_all(h)) return rc;
     const uint64_t n = h->last_n, H = h->cfg.heights, cnt = n * H;
-    bft::Params p = make_params(h, h->last_first, n);
+    bft::Params p = make_params(h, h->sets[h->last_set], h->last_first, n);
     DevMem d_out, d_len;
     HIPCHECK(h, d_out.alloc(cnt * BFTSIM_HEADER_SLOT));
     HIPCHECK(h, d_len.alloc(cnt * 4));
@@ -1451,8 +1443,7 @@ int bftsim_run(bftsim_t* h, uint64_t first, uint64_t n, bftsim_result* out) {
         if (!over || h->rcs_k >= bft::RCS_MAX_K) return BFTSIM_OK;
         const uint32_t k = 2u * h->rcs_k < bft::RCS_MAX_K ? 2u * h->rcs_k : bft::RCS_MAX_K;
         // the larger tables must fit beside everything else, or the flagged results stand (bftsim.h)
-        const uint64_t per_block = h->seg > 64 ? 1 : 64 / h->seg, blocks = (n + per_block - 1) / per_block;
-        const uint64_t grow = blocks * (bft::rcs_words(h->seg, k) - bft::rcs_words(h->seg, h->rcs_k)) * 4;
+        const uint64_t grow = launch_blocks(h, n) * (bft::rcs_words(h->seg, k) - bft::rcs_words(h->seg, h->rcs_k)) * 4;
         size_t free_b = 0, total_b = 0;
         HIPCHECK(h, hipMemGetInfo(&free_b, &total_b));
         if (grow > free_b / 10 * 9) return BFTSIM_OK;
@@ -1465,9 +1456,10 @@ int bftsim_fetch_summary(bftsim_t* h, uint64_t capacity, uint64_t* committed_hei
     if (!h) return BFTSIM_EINVAL;
     if (int rc = check_launched(h, capacity, "bftsim_fetch_summary")) return rc;
     if (int rc = sync_all(h)) return rc;                // the hash pass may run on its own stream
+    const bftsim::RowSet& r = h->sets[h->last_set];
     uint64_t n = h->last_n;
     if (tip_hash) {
-        bft::Params p = make_params(h, h->last_first, n);
+        bft::Params p = make_params(h, r, h->last_first, n);
         hipLaunchKernelGGL(bft::bft_tip_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, h->last_stream, p,
                            h->d_tips);
         HIPCHECK(h, hipGetLastError());
@@ -1475,12 +1467,12 @@ int bftsim_fetch_summary(bftsim_t* h, uint64_t capacity, uint64_t* committed_hei
     HIPCHECK(h, hipStreamSynchronize(h->last_stream));
     if (committed_height) {
         std::vector<uint32_t> ch32(n);
-        HIPCHECK(h, hipMemcpy(ch32.data(), h->d_ch, n * 4, hipMemcpyDeviceToHost));
+        HIPCHECK(h, hipMemcpy(ch32.data(), r.ch, n * 4, hipMemcpyDeviceToHost));
         for (uint64_t i = 0; i < n; ++i) committed_height[i] = ch32[i];
     }
-    if (flags) HIPCHECK(h, hipMemcpy(flags, h->d_flags, n * 4, hipMemcpyDeviceToHost));
-    if (ticks) HIPCHECK(h, hipMemcpy(ticks, h->d_ticks, n * 4, hipMemcpyDeviceToHost));
-    if (views) HIPCHECK(h, hipMemcpy(views, h->d_views, n * 8, hipMemcpyDeviceToHost));
+    if (flags) HIPCHECK(h, hipMemcpy(flags, r.flags, n * 4, hipMemcpyDeviceToHost));
+    if (ticks) HIPCHECK(h, hipMemcpy(ticks, r.ticks, n * 4, hipMemcpyDeviceToHost));
+    if (views) HIPCHECK(h, hipMemcpy(views, r.views, n * 8, hipMemcpyDeviceToHost));
     if (tip_hash) HIPCHECK(h, hipMemcpy(tip_hash, h->d_tips, n * 32, hipMemcpyDeviceToHost));
     return BFTSIM_OK;
 }
@@ -1526,17 +1518,18 @@ int bftsim_comm_init(bftsim_t* h, int world_size, int rank, const uint8_t unique
 int bftsim_stats_allreduce(bftsim_t* h, bftsim_stats* out) {
     if (!h || !out) return BFTSIM_EINVAL;
     if (!h->comm) return fail(h, BFTSIM_EINVAL, "bftsim_comm_init not called");
-    if (h->last_n == 0 || !h->d_ch) return fail(h, BFTSIM_EINVAL, "nothing launched");
+    if (h->last_n == 0) return fail(h, BFTSIM_EINVAL, "nothing launched");
     static_assert(sizeof(bftsim_stats) == (11 + bft::HIST_BINS) * 8, "bftsim_stats: a flat array of uint64 counts");
     HIPCHECK(h, hipSetDevice(h->device));
-    bft::Params p = make_params(h, h->last_first, h->last_n);
+    bft::Params p = make_params(h, h->sets[h->last_set], h->last_first, h->last_n);
     hipStream_t s = h->last_stream;
     HIPCHECK(h, hipMemsetAsync(h->d_stats, 0, 16 * 8, s));
     uint32_t g = (uint32_t)((h->last_n + 255) / 256);
     hipLaunchKernelGGL(bft::bft_stats_kernel, dim3(g), dim3(256), 0, s, p, h->d_stats);
     HIPCHECK(h, hipGetLastError());
     HIPCHECK(h, hipMemcpyAsync(h->d_red, h->d_stats, 11 * 8, hipMemcpyDeviceToDevice, s));
-    HIPCHECK(h, hipMemcpyAsync(h->d_red + 11, h->d_hist, bft::HIST_BINS * 8, hipMemcpyDeviceToDevice, s));
+    HIPCHECK(h, hipMemcpyAsync(h->d_red + 11, h->sets[h->last_set].hist, bft::HIST_BINS * 8, hipMemcpyDeviceToDevice,
+                               s));
     Rccl& r = rccl();
     ncclResult_t e;
     {
@@ -1755,7 +1748,7 @@ int bftsim_crypto_verify(bftsim_t* h, bftsim_crypto_report* out, uint64_t capaci
     HIPCHECK(h, hipMemsetAsync(a.ncm, 0, 4, s));
     HIPCHECK(h, hipMemsetAsync(a.inst_ck, 0, n * 32, s));
     HIPCHECK(h, hipMemsetAsync(a.counts, 0, 64, s));
-    bft::Params p = make_params(h, h->last_first, n);
+    bft::Params p = make_params(h, h->sets[h->last_set], h->last_first, n);
     if (M) {
         // the votes of the last verify go first: whatever fails below, bftsim_export_ledger finds none
         (void)hipFree(h->d_vsig); (void)hipFree(h->d_vhas);
@@ -1836,7 +1829,7 @@ int bftsim_export_ledger(bftsim_t* h, uint64_t capacity, uint8_t* hdr, uint64_t 
     if (slot_bytes < bftsim_ledger_slot_bytes(h->cfg.n)) return fail(h, BFTSIM_EINVAL, "slot_bytes too small");
     if (int rc = sync_all(h)) return rc;
     const uint64_t n = h->last_n, H = h->cfg.heights, cnt = n * H;
-    bft::Params p = make_params(h, h->last_first, n);
+    bft::Params p = make_params(h, h->sets[h->last_set], h->last_first, n);
     DevMem d_out, d_len;
     HIPCHECK(h, d_out.alloc(cnt * slot_bytes));
     HIPCHECK(h, d_len.alloc(cnt * 4));
@@ -1890,7 +1883,7 @@ int trace_size_pass(bftsim* h) {
     HIPCHECK(h, tmp.alloc(tb ? tb : 16));
     HIPCHECK(h, ev.create(2));
     std::vector<uint64_t> ioff(n + 1);
-    bft::Params p = make_params(h, h->last_first, n);
+    bft::Params p = make_params(h, h->sets[h->last_set], h->last_first, n);
     HIPCHECK(h, hipEventRecord(ev[0], s));
     if (h->trace_has_twins)
         hipLaunchKernelGGL(bft::bft_trace_size_kernel<true>, dim3((uint32_t)((M + 1 + 63) / 64)), dim3(64), 0, s, p,
@@ -1922,7 +1915,7 @@ int trace_emit(bftsim* h, const char* what, uint64_t m0, uint64_t m1, uint8_t* d
     HIPCHECK(h, hipMemsetAsync(d_err, 0, 4, s));
     if (t0) HIPCHECK(h, hipEventRecord(t0, s));
     if (m1 > m0) {
-        bft::Params p = make_params(h, h->last_first, h->trace_n);
+        bft::Params p = make_params(h, h->sets[h->last_set], h->last_first, h->trace_n);
         if (h->trace_has_twins)
             hipLaunchKernelGGL(bft::bft_trace_emit_kernel<true>, dim3((uint32_t)((m1 - m0 + 63) / 64)), dim3(64), 0, s, p,
                                h->trace_args, m0, m1, h->d_tfoff, d_out, d_err, bft::TwinOpt<true>{h->twin_args});
@@ -2032,9 +2025,9 @@ int bftsim_trace_twins_last_ms(bftsim_t* h, float* index_ms, float* digest_ms, f
 
 int bftsim_stats_get(bftsim_t* h, bftsim_stats* out) {
     if (!h || !out) return BFTSIM_EINVAL;
-    if (h->last_n == 0 || !h->d_ch) return fail(h, BFTSIM_EINVAL, "nothing launched");
+    if (h->last_n == 0) return fail(h, BFTSIM_EINVAL, "nothing launched");
     HIPCHECK(h, hipSetDevice(h->device));
-    bft::Params p = make_params(h, h->last_first, h->last_n);
+    bft::Params p = make_params(h, h->sets[h->last_set], h->last_first, h->last_n);
     HIPCHECK(h, hipMemsetAsync(h->d_stats, 0, 16 * 8, h->last_stream));
     uint32_t g = (uint32_t)((h->last_n + 255) / 256);
     hipLaunchKernelGGL(bft::bft_stats_kernel, dim3(g), dim3(256), 0, h->last_stream, p, h->d_stats);
@@ -2042,7 +2035,7 @@ int bftsim_stats_get(bftsim_t* h, bftsim_stats* out) {
     unsigned long long st[16];
     uint64_t hist[bft::HIST_BINS];
     HIPCHECK(h, hipMemcpyAsync(st, h->d_stats, sizeof st, hipMemcpyDeviceToHost, h->last_stream));
-    HIPCHECK(h, hipMemcpyAsync(hist, h->d_hist, sizeof hist, hipMemcpyDeviceToHost, h->last_stream));
+    HIPCHECK(h, hipMemcpyAsync(hist, h->sets[h->last_set].hist, sizeof hist, hipMemcpyDeviceToHost, h->last_stream));
     HIPCHECK(h, hipStreamSynchronize(h->last_stream));
     out->instances = st[0];
     out->committed_heights = st[1];

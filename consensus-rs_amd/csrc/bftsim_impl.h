@@ -25,14 +25,7 @@ struct bftsim {
     uint64_t cap_inst = 0;
     uint8_t* d_addr = nullptr;
     uint8_t* d_ghash = nullptr;
-    uint32_t* d_ch = nullptr;
-    uint32_t* d_flags = nullptr;
-    uint32_t* d_ticks = nullptr;
-    uint64_t* d_views = nullptr;
-    uint32_t* d_rec = nullptr;
-    uint8_t* d_hash = nullptr;
     unsigned long long* d_stats = nullptr;
-    uint64_t* d_hist = nullptr;       // [HIST_BINS] of the last launch
     uint64_t* d_red = nullptr;        // bftsim_stats image reduced by bftsim_stats_allreduce
     uint4* d_evict = nullptr;         // attribution pass only (bft_l2_evict_kernel): 64 MiB of zeros
     bool pmc_evict = false;
@@ -71,12 +64,7 @@ struct bftsim {
     float audit_ms[4] = {0, 0, 0, 0}; // decode, recoveries, classify + tally, copies of the last audit (SPEC.md §11c)
     float ledger_ms[4] = {0, 0, 0, 0};// decode, recoveries, tally + link, copies of the last bftsim_verify_ledger (§11d)
     uint8_t* d_tips = nullptr;        // [cap_inst * 32]
-    uint32_t* d_rcs = nullptr;        // RoundChangeSet tables, rcs_words(seg) per wave / workgroup
-    uint32_t* d_backlog = nullptr;    // replay mode: backlog slots, backlog_words(seg) per wave / workgroup
     uint64_t backlog_bytes = 0;
-    uint32_t* d_resume = nullptr;     // FAST launches: [cap_inst] hand-over flags
-    uint32_t* d_resume_q = nullptr;   // FAST launches: [2 + cap_inst] the resume kernel's queue
-    uint32_t* d_save = nullptr;       // FAST launches: [SAVE_WORDS][cap_inst * 64] saved lane state
     int fast = 1;                     // FAST kernel + resume for N = 64 (bftsim_set_fast(h, 0): full kernel)
     uint32_t window = 0;              // 0: full per-height rows; else ring of `window` rows
     uint32_t rcs_k = bft::RCS_DEFAULT_K;   // RoundChangeSet rounds per validator (bftsim_set_rcs_capacity)
@@ -85,7 +73,11 @@ struct bftsim {
     uint32_t trace_ticks = 0;
     uint64_t n_req = 0;               // instances of the next launch (bftsim_prepare); <= cap_inst
     uint64_t last_n = 0, last_first = 0;
+    uint32_t last_set = 0;            // the row-table set of the last launch
     hipStream_t last_stream = nullptr;
+    // Every device buffer of a launch belongs to a row-table set (RowSet): bftsim_prepare allocates sets[0 .. n_sets),
+    // n_sets = max(1, pipeline), and free_bufs releases them; the handle holds no pointer into a set. An unpipelined
+    // launch runs on set 0; whatever reads a launch's results reads sets[last_set].
     // Pipelined launches (bftsim_set_pipeline(h, D), the batch-throughput mode): a ring of D row-table sets,
     // each with the scratch of one launch, so that up to D launches are in flight at once.
     //   * the consensus kernel (+ resume + suffix rows) of each launch runs on one of `n_cs` launch streams
@@ -105,10 +97,16 @@ struct bftsim {
         // recorded block differs from its prediction [n]
         uint64_t* byz = nullptr; uint32_t* bad = nullptr;
         uint32_t* pred = nullptr;     // [n][H] the predicted block of each height (bft_spec_suffix_kernel)
-        // a launch's own scratch (set 0: the handle's buffers)
-        uint64_t* hist = nullptr; uint32_t* rcs = nullptr; uint32_t* backlog = nullptr;
-        uint32_t* resume = nullptr; uint32_t* save = nullptr; uint32_t* resume_q = nullptr;
-        uint32_t* hint = nullptr;     // host-mapped: the hand-over count of the set's last launch (resume grid)
+        // a launch's own scratch
+        uint64_t* hist = nullptr;     // [HIST_BINS]
+        uint32_t* rcs = nullptr;      // RoundChangeSet tables, rcs_words(seg) per wave / workgroup
+        uint32_t* backlog = nullptr;  // replay mode: backlog slots, backlog_words(seg) per wave / workgroup
+        // FAST launches (N = 64): [n] hand-over flags, [2 + n] the resume kernel's queue, [SAVE_WORDS][n * 64] saved
+        // lane state
+        uint32_t* resume = nullptr; uint32_t* resume_q = nullptr; uint32_t* save = nullptr;
+        // host-mapped: the hand-over count of the set's last launch (resume grid). Like the events it lives until
+        // bftsim_destroy: a grid estimate that outlasts the buffers
+        uint32_t* hint = nullptr;
         hipEvent_t done = nullptr;    // hash pass of the last launch that used the set
         hipEvent_t batch_done = nullptr;   // or: the event of the chain batch that hashed it (flush_batch)
         hipEvent_t entry = nullptr;   // the caller's stream at the launch call
@@ -140,7 +138,7 @@ struct bftsim {
     bool seed_spec = true;            // little-endian seeds, N = 64: predicted blocks (BFTSIM_TESTING + BFTSIM_SEED_SPEC=0: off)
     int pipeline = 0;                 // number of row-table sets (0: no pipelining)
     uint32_t sfx_rows = 0;            // heights per hash-pass chunk (0: no hash pass)
-    uint32_t n_sets = 0, cur_set = 0;
+    uint32_t n_sets = 0, cur_set = 0; // allocated sets; the ring cursor of the pipelined launches
     bool last_pipe = false;           // the last launch ran on the launch streams
     hipStream_t cs[MAX_CS] = {}, hstr[MAX_HS] = {};
     uint32_t n_cs = 2, n_hs = 2, cur_cs = 0, cur_hs = 0;

@@ -88,6 +88,66 @@ def test_pipeline_toggle_and_sizes():
         sim.close()
 
 
+def test_buffer_lifecycle_on_one_handle():
+    """Everything that frees and reallocates the row-table sets, in turn on one handle: a larger prepare (every set
+    grows), the pipeline off (one set), on at another depth, another RoundChangeSet capacity, a window and back. An
+    N = 64 configuration, so the FAST launches' hand-over buffers are among what each step replaces; 70 heights, so
+    the window of 64 rows wraps. Every launch has a range of its own and each step's last launch is compared with the
+    oracle; a set that kept a freed pointer, or a reader that looked past the last launch's set, shows as wrong rows."""
+    import reuse_cases as R
+    cfg_id = "byz22"
+    cfg, n = R.config(cfg_id), R.instances(cfg_id)
+    assert cfg.n == 64 and cfg.heights > 64
+
+    def ref(k, count=1):
+        from parity_util import FIELDS
+        return {f: np.concatenate([R.ref(cfg_id, k + j)[f] for j in range(count)]) for f in FIELDS}
+
+    def check(sim, k, what, count=1):
+        sim.sync()
+        want = ref(k, count)
+        assert sim.launched() == (k * n, count * n), what
+        assert_same(want, sim.fetch(), what)
+        assert sim.stats()["views"] == int(want["views"].sum()), what
+
+    sim = _sim(cfg)
+    try:
+        sim.set_pipeline(True, 3)
+        sim.prepare(n)
+        sim.launch(0)
+        sim.launch(n)
+        check(sim, 1, "depth 3")
+        sim.prepare(2 * n)                          # every set is freed and allocated again at twice the size
+        sim.launch(2 * n)
+        sim.launch(4 * n)
+        check(sim, 4, "depth 3, twice the instances", count=2)
+        sim.set_pipeline(False)
+        sim.prepare(n)
+        sim.launch(6 * n)
+        check(sim, 6, "pipeline off")
+        sim.set_pipeline(True, 2)
+        sim.prepare(n)
+        for k in (7, 8, 9):                         # the ring of two wraps
+            sim.launch(k * n)
+        check(sim, 9, "depth 2")
+        sim.set_rcs_capacity(40)
+        sim.prepare(n)
+        sim.launch(10 * n)
+        sim.launch(11 * n)
+        check(sim, 11, "depth 2, RoundChangeSet capacity 40")
+        got = sim.run_stream(12 * n, n, window=64)  # set_window(64), prepare, launch, fetch_summary, stats
+        want = O.run_stream(cfg, 12 * n, n, threads=8)
+        for f in ("committed_height", "flags", "ticks", "views", "tip_hash", "round_hist", "latency_hist"):
+            assert np.array_equal(want[f], got[f]), ("window 64", f)
+        sim.set_window(0)
+        sim.prepare(n)
+        sim.launch(13 * n)
+        sim.launch(14 * n)
+        check(sim, 14, "window 0 again")
+    finally:
+        sim.close()
+
+
 def _timed_run(cfg, first, n, launches=25):
     """bench.py's timed mode for n instances per GPU: the pipeline depth and hash batch it picks
     (bftsim.configs.timed_pipeline), then `launches` launches of the same instances (its 5 warmup + 20 timed

@@ -14,8 +14,8 @@ variant.
 
 Every chain kernel and mode (the settings of test_gpu_pipeline.py, which the library reads only under BFTSIM_TESTING=1
 and does not report back: they select the modes as long as bftsim.hip's knobs keep their meaning), two ring shapes,
-two drivers; alternating launch sizes; an unpipelined handle; the tip hashes and the exported headers; the general
-kernel, which clears its rows, as control."""
+two drivers; alternating launch sizes; an unpipelined handle; both drivers in turn on one handle; the tip hashes and
+the exported headers; the general kernel, which clears its rows, as control."""
 import pytest
 
 import reuse_cases as R
@@ -201,6 +201,44 @@ def test_unpipelined_handle_reuse(cfg_id):
             ref = R.ref(cfg_id, k)
             assert_same(ref, got, f"{cfg_id} unpipelined run {k}")
             assert st["views"] == int(ref["views"].sum()) and st["committed_heights"] == int(ref["committed_height"].sum())
+    finally:
+        sim.close()
+
+
+@pytest.mark.parametrize("mode", ["default", "pair-pred"])
+@pytest.mark.parametrize("cfg_id", ["drop", "crash"])
+def test_mixed_drivers_on_one_handle(cfg_id, mode, monkeypatch):
+    """pipelined launches, an unpipelined run() between them, pipelined launches again, on one handle of depth 3 and
+    hash batch 2. The run() carries a tick trace, which keeps it off the launch streams: it waits for the pipelined
+    launches before it, runs wholly on set 0 and leaves the ring's cursor alone. So the sets go 1, 2 | 0 | 0, 1, 2:
+    range 3 reuses the set of range 2 (the run's), ranges 4 and 5 those of ranges 0 and 1 -- every reused set holds
+    another range's rows, asserted first on the oracle alone. Every launch is compared whole, the run() both by what
+    it returns and by a fetch of its own."""
+    launches, trace_ticks = 6, 4
+    R.assert_reuse_preconditions(cfg_id, 3, launches)
+    for prev, new in ((2, 3), (0, 4), (1, 5)):
+        lower, differing = R.stale_counts(R.ref(cfg_id, prev), R.ref(cfg_id, new))
+        if cfg_id == "crash":
+            assert differing == R.N_INST, (cfg_id, prev, new, differing)
+        else:
+            assert lower >= R.MIN_LOWER and differing >= R.MIN_DIFFERING, (cfg_id, prev, new, lower, differing)
+    _set_mode(mode, monkeypatch)
+    n = R.instances(cfg_id)
+    cfg = R.config(cfg_id)
+    sim = _sim(cfg)
+    try:
+        sim.set_pipeline(True, 3)
+        sim.set_hash_batch(2)
+        sim.prepare(n)
+        for k in range(launches):
+            what = f"{cfg_id} {mode} mixed drivers, range {k}"
+            if k == 2:
+                got = sim.run(k * n, n, trace_ticks=trace_ticks)
+                assert got["trace"].shape == (n, trace_ticks, cfg.n)
+                assert_same(R.ref(cfg_id, k), got, what + " (run)")
+            else:
+                sim.launch(k * n)
+            _compare(sim, R.ref(cfg_id, k), what)
     finally:
         sim.close()
 
